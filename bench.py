@@ -17,14 +17,24 @@ LOCAL_RANK, WORLD_SIZE, MASTER_ADDR=127.0.0.1, a free MASTER_PORT), relays rank 
 with the first non-zero exit code of a rank (never exec). A box with fewer than N GPUs gets a JSON line with an
 "error" field and a non-zero exit code, no traceback.
 
-After the main line is complete, under a watchdog (they can never cost the measurement), every leg agreeing
-across ranks that its set-up succeeded before any timed collective is entered:
+A plain run sets up, warms up (the W warm-up steps, then --preheat-s seconds of back-to-back steps for steady clocks),
+times the --steps steps, writes the last step's output with --dump-outputs DIR and prints the line: the headline
+fields and a roofline block priced on the engine's own event times of the timed steps. Everything below that takes
+runs of its own (the extras, the post-measurement legs at N > 1, the box calibration kernel, the shader-clock
+sampling, the CPU baselines) runs with --full only.
+
+--dump-outputs DIR: DIR/output_sample.npy is a fixed seeded sample of the output of the last timed step, the
+[channels, windows x window_out_len] f32 layout a caller of the path receives (at N > 1 gathered from the ranks'
+shards onto rank 0), at the positions in DIR/output_positions.npy (f64, the same for every run and build).
+
+With --full, after the main line is complete, under a watchdog (they can never cost the measurement), every leg
+agreeing across ranks that its set-up succeeded before any timed collective is entered:
   config.weak        - ONE stereo job of N x L samples per channel cut the same way (per-GPU work that of N = 1)
   config.ref_1gpu    - the fixed job on every rank's own GPU alone, in this run (max over ranks)
   config.c5_sharded  - BASELINE configs[4] (8 channels, window 65536) cut over the same ranks
   config.concat      - the path's one optional collective: the RCCL concat of the shards on rank 0
 
-The same JSON line carries
+The same JSON line carries (box calibration, clock under load and measured copy bandwidth with --full only)
   roofline     - the dominant kernel (the N = 16384 fused hop kernel) priced on SURVEY 8(d4)'s
                  algorithmic READ bytes 4*N per hop of rank 0's launch against the 8 TB/s HBM peak; its duration
                  is the MEDIAN of the per-launch HIP-event times the engine records around the kernel itself
@@ -329,9 +339,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--preheat-s", type=float, default=2.0,
                     help="seconds of back-to-back launches before the timed steps (steady DVFS state)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: box calibration, clock under load, the extras, "
+                         "the post-measurement legs (N > 1) and the CPU baselines (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed seeded sample of the last timed step's output to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the copy microbench, the PCIe-inclusive runs and the post-measurement legs")
+                    help="with --full: skip the copy microbench, the PCIe-inclusive runs and the post-measurement legs")
     args = ap.parse_args()
     if args.gpus < 1 or args.steps < 1:
         print(json.dumps(error_line(args, "--gpus and --steps must be >= 1")))
@@ -478,7 +493,8 @@ def worker(args, say):
             step()
         # pre-heat: >= preheat_s of back-to-back launches so the timed steps run at the clock the chip
         # holds under this load (MI355X_MICROARCH.md, DVFS), not at the boost clock of an idle chip
-        clk_thread.start()
+        if args.full:
+            clk_thread.start()
         t_heat = time.perf_counter()
         n_heat = 0
         while time.perf_counter() - t_heat < args.preheat_s:
@@ -488,7 +504,8 @@ def worker(args, say):
             stream.synchronize()
         t_heat_end = time.perf_counter()
         clk_stop.set()
-        clk_thread.join(timeout=2.0)
+        if args.full:
+            clk_thread.join(timeout=2.0)
         for _ in range(8):  # the join above left the chip idle for a moment
             step()
         barrier()
@@ -519,21 +536,32 @@ def worker(args, say):
     sclk_mhz = statistics.median(clk_under_load) if clk_under_load else None
     dt = max_over_ranks(dt)
 
+    if args.dump_outputs:
+        def sum_over_ranks(t):
+            if dist is None:
+                return t
+            t = t.to(red_device)
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            return t
+
+        dump_outputs(torch, args.dump_outputs, rank, mine, bufs, wout, nwin, device, sum_over_ranks)
+
     # ---- box calibration: a fixed pure-VALU kernel on the same stream right after the timed
     # steps, ~50 ms, so that a slow box shows in the JSON line itself
     calib = None
-    try:
-        import ctypes as C
+    if args.full:
+        try:
+            import ctypes as C
 
-        ms_l, ns_i = C.c_float(0), C.c_float(0)
-        rc = _lib.lib().rc_calib_valu(dev_index, C.c_void_p(stream.cuda_stream), 48, C.byref(ms_l), C.byref(ns_i))
-        if rc == 0:
-            calib = {"ms_per_launch": float(ms_l.value), "ns_per_inst": float(ns_i.value)}
-    except Exception as ex:  # noqa: BLE001
-        calib = {"error": f"{type(ex).__name__}: {ex}"[:200]}
+            ms_l, ns_i = C.c_float(0), C.c_float(0)
+            rc = _lib.lib().rc_calib_valu(dev_index, C.c_void_p(stream.cuda_stream), 48, C.byref(ms_l), C.byref(ns_i))
+            if rc == 0:
+                calib = {"ms_per_launch": float(ms_l.value), "ns_per_inst": float(ns_i.value)}
+        except Exception as ex:  # noqa: BLE001
+            calib = {"error": f"{type(ex).__name__}: {ex}"[:200]}
 
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         with torch.cuda.stream(stream):
             # device copy microbench on this very GPU: the measured bandwidth the roofline is also priced on
             n_copy = 1 << 28  # 1 GiB of f32
@@ -676,7 +704,7 @@ def worker(args, say):
         if "seam" in extras:
             res["config"]["streaming_seam"] = extras["seam"].get("streaming_seam")
             res["config"]["live_latency_us"] = extras["seam"].get("live_latency_us")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             one, many = cpu_baselines()
             res["cpu_baseline"] = one
             res["config"]["x_cpu"] = round(value / one["value"], 1)
@@ -752,7 +780,7 @@ def worker(args, say):
         barrier()
         return max_over_ranks(time.perf_counter() - t) / k
 
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         timer.start()
         ks = max(args.steps, 20)
 
@@ -849,6 +877,34 @@ def worker(args, say):
         dist.destroy_process_group()
     timer.cancel()
     return 0
+
+
+DUMP_PER_CHANNEL = 1 << 21  # sampled output positions per channel: 2 x 8 MiB of f32 values + 16 MiB of positions
+DUMP_SEED = 0xD0D0
+
+
+def dump_outputs(torch, out_dir, rank, mine, bufs, wout, nwin, device, sum_over_ranks):
+    """--dump-outputs: the output of the last timed step at a fixed seeded sample of positions of the
+    [CHANNELS, nwin * wout] layout, the same positions in every channel. Each rank fills the positions its shards hold;
+    the ranks' parts are summed (each position lies in exactly one shard, the others add zeros) and rank 0 writes
+    output_sample.npy (f32 [CHANNELS, k]) and output_positions.npy (f64 [k])."""
+    import numpy as np
+
+    n = nwin * wout
+    k = min(DUMP_PER_CHANNEL, n)
+    pos = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+    pos_d = torch.from_numpy(pos).to(device)
+    vals = torch.zeros((CHANNELS, k), dtype=torch.float32, device=device)
+    for s in mine:
+        lo, hi = s.win_first * wout, (s.win_first + s.win_count) * wout
+        a, b = int(np.searchsorted(pos, lo)), int(np.searchsorted(pos, hi))
+        if b > a:
+            vals[s.ch_first:s.ch_first + s.ch_count, a:b] = bufs[s][:, pos_d[a:b] - lo]
+    vals = sum_over_ranks(vals)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "output_sample.npy"), vals.cpu().numpy())
+        np.save(os.path.join(out_dir, "output_positions.npy"), pos.astype(np.float64))
 
 
 def e2e_host(eng, x, torch):

@@ -93,3 +93,33 @@ def test_launcher_stopped_by_a_signal_takes_its_ranks_with_it(tmp_path, sig):
                  open(f"/proc/{q}/stat").read().rsplit(")", 1)[1].split()[0] != "Z"]
         time.sleep(0.1)
     assert not alive, f"ranks {alive} outlived the launcher"
+
+
+@pytest.mark.parametrize("world", [1, 2, 3, 8])
+def test_dump_outputs_gathers_the_same_sample_from_any_shard_plan(tmp_path, world):
+    """--dump-outputs: every rank fills the sampled positions its shards hold, the parts are summed across the ranks;
+    at any N the result is the sample of the whole [channels, windows x window_out_len] layout, at positions that are
+    the same in every run. Host tensors stand in for the device buffers."""
+    import numpy as np
+    import torch
+
+    import bench
+    from rocoder_amd.distributed import shard_plan
+
+    wout, nwin = 64, 50_000
+    full = torch.randn((bench.CHANNELS, nwin * wout), generator=torch.Generator().manual_seed(1))
+    plan = shard_plan(bench.CHANNELS, nwin, world)
+    parts = []
+    for r in range(world):
+        mine = [s for s in plan if s.rank == r]
+        bufs = {s: full[s.ch_first:s.ch_first + s.ch_count,
+                        s.win_first * wout:(s.win_first + s.win_count) * wout].clone() for s in mine}
+        bench.dump_outputs(torch, str(tmp_path / str(r)), 0, mine, bufs, wout, nwin, "cpu",
+                           lambda v: parts.append(v) or v)
+    total = sum(parts)
+    pos = np.load(tmp_path / "0" / "output_positions.npy")
+    assert pos.dtype == np.float64 and len(pos) == bench.DUMP_PER_CHANNEL and np.all(np.diff(pos) > 0)
+    assert torch.equal(total, full[:, torch.from_numpy(pos.astype(np.int64))])
+    if world == 1:
+        sample = np.load(tmp_path / "0" / "output_sample.npy")
+        assert sample.dtype == np.float32 and np.array_equal(sample, total.numpy())

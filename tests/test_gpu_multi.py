@@ -184,7 +184,7 @@ def test_rccl_one_rank_walks_the_sharded_concat():
 
 @pytest.mark.gpu
 def test_bench_rehearsal_survives_a_leg_that_fails_on_one_rank():
-    """bench.py --gpus 2 without a launcher (it starts its own ranks), both ranks on this one GPU over gloo
+    """bench.py --gpus 2 --full without a launcher (it starts its own ranks), both ranks on this one GPU over gloo
     (ROCODER_BENCH_REHEARSAL=1), with the set-up of the `weak` leg failing on rank 1 only: the ranks agree to skip that
     leg's timed collectives (a rank that skipped its barriers alone hung the others), the main line is
     printed with the error inside config.weak, the later legs still run, exit code 0."""
@@ -196,7 +196,7 @@ def test_bench_rehearsal_survives_a_leg_that_fails_on_one_rank():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--preheat-s", "0.3"], env=env, capture_output=True, text=True, timeout=420)
+                        "--preheat-s", "0.3", "--full"], env=env, capture_output=True, text=True, timeout=420)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-500:], r.stderr[-2000:])
     res = json.loads(lines[0])
@@ -205,3 +205,37 @@ def test_bench_rehearsal_survives_a_leg_that_fails_on_one_rank():
     assert "error" in cfg["weak"], cfg["weak"]
     assert "ms_per_step_1gpu" in cfg["ref_1gpu"] and "ms_per_step" in cfg["c5_sharded"], cfg
     assert "legs_error" not in cfg
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_is_the_same_at_one_and_two_ranks(tmp_path):
+    """A plain bench run (no --full) runs the headline only, and --dump-outputs writes the sample of the last timed
+    step's output; the same job cut over two ranks (a rehearsal: both on this GPU over gloo) gathers the same values
+    from its shards."""
+    import json
+    import sys
+
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "ROCODER_BENCH_REHEARSAL"):
+        env.pop(k, None)
+    dumps = {}
+    for n in (1, 2):
+        d = tmp_path / f"gpus{n}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2",
+                            "--warmup", "1", "--preheat-s", "0.3", "--dump-outputs", str(d)],
+                           env=dict(env, ROCODER_BENCH_REHEARSAL="1") if n > 1 else env,
+                           capture_output=True, text=True, timeout=420)
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, (n, r.returncode, r.stdout[-500:], r.stderr[-2000:])
+        res = json.loads(lines[0])
+        assert res["n_gpus"] == n and res["steps"] == 2 and res["value"] > 0 and res["ms_per_step"] > 0
+        assert "cpu_baseline" not in res and "other_configs" not in res["config"] and "weak" not in res["config"]
+        files = sorted(os.listdir(d))
+        assert files == ["output_positions.npy", "output_sample.npy"], files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        sample, pos = np.load(d / "output_sample.npy"), np.load(d / "output_positions.npy")
+        assert sample.dtype == np.float32 and pos.dtype == np.float64 and sample.shape == (2, len(pos))
+        assert np.all(np.isfinite(sample)) and float(np.sqrt(np.mean(sample.astype(np.float64) ** 2))) > 0.01
+        dumps[n] = (sample, pos)
+    assert np.array_equal(dumps[1][1], dumps[2][1])
+    assert np.array_equal(dumps[1][0], dumps[2][0])

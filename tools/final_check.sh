@@ -6,7 +6,7 @@
 source tools/gpu_steps.sh
 step 1100 final_tests_gpu python -m pytest tests -q -x -m gpu
 step 300 final_smoke python __graft_entry__.py smoke
-step 400 final_bench python bench.py
+step 400 final_bench python bench.py --full
 grep -h '^{' gpurun_out/final_bench.log > gpurun_out/final_bench.json
 if ! grep -q '^{' gpurun_out/final_bench.json; then echo "[final_bench printed no JSON line]"; FAIL=1; fi
 finish

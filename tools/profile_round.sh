@@ -8,6 +8,7 @@
 #   <tag>_pmc_summary.txt     separate --pmc passes, mean per hop-kernel launch, headed by `kernel_id:`
 # usage (from the repo root on the box): tools/profile_round.sh r02a [pmc]   -> gpurun_out/<tag>/
 set -u
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 TAG=$1
 WITH_PMC=${2:-pmc}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
@@ -15,7 +16,7 @@ mkdir -p $OUT
 STEPS=20
 BENCH="$GRAFT_REPO_ROOT/bench.py --steps $STEPS --warmup 5 --no-cpu-baseline --no-extras"
 cd /tmp && export TMPDIR=/tmp
-python3 $GRAFT_REPO_ROOT/bench.py --steps $STEPS --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/bench.err
+python3 "$REPO/bench.py" --full --steps $STEPS --warmup 5 > "$OUT/${TAG}_bench.json" 2> "$OUT/bench.err"
 echo "bench rc=$?"; cut -c1-400 $OUT/${TAG}_bench.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $BENCH > $OUT/trace.log 2>&1
 echo "trace rc=$?"
