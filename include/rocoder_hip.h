@@ -52,7 +52,7 @@ typedef int (*rc_freq_kernel)(uint64_t time_ms, const float *in_reim, float *out
 /* Stretcher::new arguments (src/stretcher.rs:30-39) + main.rs:131-147 call-site values. */
 typedef struct rc_config {
     uint32_t struct_size;    /* = sizeof(rc_config), ABI guard */
-    uint32_t window_len;     /* -w/--window (src/main.rs:34); even, 4..65536 (powers of two: the fast kernels) */
+    uint32_t window_len;     /* -w/--window (src/main.rs:34); even, 4..4194304 (powers of two <= 65536: the fast kernels; above 65536: the long-window path); odd or larger: RC_EUNSUPPORTED */
     float factor;            /* -f/--factor (src/main.rs:46-52) */
     float amplitude;         /* -a/--amplitude */
     int32_t pitch_multiple;  /* -p/--pitch_multiple, i8 in the reference, != 0 */

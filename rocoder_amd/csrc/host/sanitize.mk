@@ -21,13 +21,13 @@ all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../b
 # streaming seam) host-only over tests/c/hip_stub.cpp - a HIP runtime whose device memory is host memory and whose
 # kernels compute nothing - driven by tests/c/engine_host_driver.cpp:
 #   ../../bin/engine_asan : -fsanitize=address,undefined      ../../bin/engine_tsan : -fsanitize=thread
-ENGINE_SRC := ../rc_engine.cpp $(ROOT)/tests/c/hip_stub.cpp $(ROOT)/tests/c/engine_host_driver.cpp
+ENGINE_SRC := ../rc_engine.cpp $(ROOT)/tests/c/hip_stub.cpp $(ROOT)/tests/c/hip_stub_long.cpp $(ROOT)/tests/c/engine_host_driver.cpp
 ENGINE_FLAGS := -g -O1 -std=c++17 -Wall -Wno-unused-function -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -DRC_PMAX=32 \
     -I/opt/rocm/include -x c++
-../../bin/engine_asan: $(ENGINE_SRC) ../rc_kernels.h $(ROOT)/include/rocoder_hip.h
+../../bin/engine_asan: $(ENGINE_SRC) ../rc_kernels.h ../rc_long.h $(ROOT)/include/rocoder_hip.h
 	mkdir -p ../../bin
 	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(ENGINE_FLAGS) $(ENGINE_SRC) -o $@ -lpthread
-../../bin/engine_tsan: $(ENGINE_SRC) ../rc_kernels.h $(ROOT)/include/rocoder_hip.h
+../../bin/engine_tsan: $(ENGINE_SRC) ../rc_kernels.h ../rc_long.h $(ROOT)/include/rocoder_hip.h
 	mkdir -p ../../bin
 	$(CXX) -fsanitize=thread $(ENGINE_FLAGS) $(ENGINE_SRC) -o $@ -lpthread
 .PHONY: all
