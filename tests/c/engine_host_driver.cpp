@@ -46,6 +46,11 @@ static rc_config config(uint32_t N, float f, int p, uint32_t ch) {
     c.channels = (uint16_t)ch;
     c.buffer_secs = 1.0f;
     c.seed = 7;
+    c.dk_gain = 0.5f;  // (the device kernel's settings: read only when device_kernel is set)
+    c.dk_gain_outside = 0.25f;
+    c.dk_lo_bin = 8;
+    c.dk_hi_bin = N / 8;
+    c.dk_shift_bins = 3;
     return c;
 }
 static std::vector<std::vector<float>> input(uint32_t ch, size_t L) {
@@ -55,9 +60,12 @@ static std::vector<std::vector<float>> input(uint32_t ch, size_t L) {
     return x;
 }
 
-static void offline(uint32_t N, float f, int p, uint32_t ch, size_t L, rc_freq_kernel k, uint32_t kthreads) {
+// dk: a curated device kernel; launches: if non-zero, what rc_engine_last_kernel_stats must report for the calls
+static void offline(uint32_t N, float f, int p, uint32_t ch, size_t L, rc_freq_kernel k, uint32_t kthreads,
+                    uint32_t dk = RC_DK_NONE, uint32_t launches = 0) {
     rc_config c = config(N, f, p, ch);
     float gain = 2.0f;
+    c.device_kernel = dk;
     c.kernel = k;
     c.kernel_user = &gain;
     c.kernel_threads = kthreads;
@@ -102,6 +110,26 @@ static void offline(uint32_t N, float f, int p, uint32_t ch, size_t L, rc_freq_k
     float ms[8];
     size_t nms = 0;
     CHECK(rc_engine_kernel_times(e, ms, 8, &nms) == RC_OK);
+    uint32_t got_launches = 0;
+    CHECK(rc_engine_last_kernel_stats(e, nullptr, nullptr, &got_launches) == RC_OK);
+    CHECK(launches == 0 || got_launches == launches);
+    rc_engine_destroy(e);
+}
+
+// the single-hop entry points (the ReFFT seam): forward transform, then a resynthesis through the host or device kernel
+static void single_hop(uint32_t N, uint32_t dk, rc_freq_kernel k) {
+    rc_config c = config(N, 2.0f, 1, 2);
+    float gain = 2.0f;
+    c.device_kernel = dk;
+    c.kernel = k;
+    c.kernel_user = &gain;
+    rc_engine *e = nullptr;
+    CHECK(rc_engine_create(&c, &e) == RC_OK);
+    std::vector<float> x(N, 0.25f), spec((size_t)N * 2), y(N);
+    for (uint64_t hop = 0; hop < 2; ++hop) {
+        CHECK(rc_engine_forward_fft(e, x.data(), spec.data()) == RC_OK);
+        CHECK(rc_engine_resynth(e, 1, hop, x.data(), y.data()) == RC_OK);
+    }
     rc_engine_destroy(e);
 }
 
@@ -268,7 +296,26 @@ int main() {
     offline(1000, 4.0f, 2, 2, 30000, gain_kernel, 2);
     offline(4096, 2.0f, -3, 2, 60000, gain_kernel, 2);
     offline(1024, 4.0f, 1, 2, 30000, panicking_kernel, 2);
+    // windows above 65536: a power of two and a chirp-z length, plain and through a host kernel
+    offline(131072, 2.0f, 1, 2, 400000, nullptr, 0);
+    offline(100002, 2.0f, 1, 1, 300000, nullptr, 0);
+    offline(131072, 2.0f, 1, 1, 400000, gain_kernel, 2);
+    offline(100002, 2.0f, 1, 2, 300000, gain_kernel, 1);
     CHECK(g_calls.load() > 0);
+    // curated device kernels and the single-hop calls at one length of each window path. Launches of an offline call:
+    // analysis, device kernel, synthesis, overlap-add (2); RC_DK_GAIN rides on the amplitude: the plain stretch's
+    const struct {
+        uint32_t N;
+        size_t L;
+        uint32_t band_shift, gain;
+    } paths[] = {{4096, 30000, 5, 1}, {32768, 150000, 7, 1}, {3000, 20000, 6, 5}, {131072, 400000, 6, 3}};
+    for (const auto &t : paths) {
+        offline(t.N, 2.0f, 1, 2, t.L, nullptr, 0, RC_DK_BAND, t.band_shift);
+        offline(t.N, 2.0f, 1, 2, t.L, nullptr, 0, RC_DK_SHIFT, t.band_shift);
+        offline(t.N, 2.0f, 1, 2, t.L, nullptr, 0, RC_DK_GAIN, t.gain);
+        for (uint32_t dk : {RC_DK_NONE, RC_DK_GAIN, RC_DK_BAND, RC_DK_SHIFT}) single_hop(t.N, dk, nullptr);
+        single_hop(t.N, RC_DK_NONE, gain_kernel);
+    }
     // the streaming seam: copies and views, small batches (look-ahead changes blocks often), one and several channels
     for (int view = 0; view < 2; ++view) {
         seam(1024, 4.0f, 1, 2, 90000, 8, view);
