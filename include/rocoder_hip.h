@@ -207,6 +207,36 @@ int rc_engine_forward_fft(rc_engine *e, const float *samples, float *out_reim);
 int rc_engine_resynth(rc_engine *e, uint32_t channel, uint64_t hop, const float *samples,
                       float *out);
 
+/* ---- user device kernels: a frequency kernel written in HIP, compiled at run time ----------------------------
+ * The GPU-resident form of the reference's hot-swapped apply() (README.md "Live coding", src/fft.rs:76-108,
+ * src/hotswapper.rs). The user's source defines one function,
+ *   __device__ float2 rc_apply(const rc_spectrum &X, uint32_t j, const rc_hop &h);   returns Y[j]
+ * which runs for every output bin j of every hop between the forward transform and the resynthesis, on the device:
+ *   X         the hop's N-bin spectrum in natural DFT order, read-only; X[i] is X[i mod N] for ANY integer i
+ *   h.n       N;  h.channel, h.hop: the channel and hop index k (the k of rc_phase_key)
+ *   h.time_ms rc_config::kernel_time_ms when non-zero, else the wall clock when the launch was enqueued: one value per
+ *             launch, not per hop (the reference reads the clock per hop)
+ *   h.param(i) the i-th of up to 16 float params (rc_*_set_device_kernel_params), 0 past n_params
+ * The engine owns the prelude that defines rc_spectrum / rc_hop and the wrapper kernel rc_user_dk; rc_apply writes only
+ * its return value and must terminate (a kernel cannot be preempted). Compiled with --offload-arch=gfx950 -O3 -std=c++17,
+ * no fast-math. Diagnostics name rc_user_dk.hip:<line>, or the file a leading `#line 1 "name"` line names. A user device
+ * kernel excludes rc_config::kernel and rc_config::device_kernel. Compiling and loading are separate steps, as the
+ * reference compiles on its watcher thread and loads on the DSP thread (src/hotswapper.rs:19-30, src/fft.rs:78). */
+/* Pure host, no device, thread-safe: HIP source -> gfx950 code object. *code_len is always set (code NULL: a size
+ * query, RC_ECAPACITY). RC_ECAPACITY: code_cap too small; RC_EINVAL: the source does not compile or defines no rc_apply
+ * (the compiler log in `log`, NUL-terminated and cut to log_cap; its first error line in rc_last_error());
+ * RC_EUNSUPPORTED: hiprtc cannot be loaded. */
+int rc_dk_compile(const char *src, size_t src_len, char *code, size_t code_cap, size_t *code_len,
+                  char *log, size_t log_cap);
+/* Loads a code object from rc_dk_compile; it runs from the next call on (code NULL: remove the kernel). The bytes are
+ * checked first (ELF64, EM_AMDGPU, gfx950, an rc_user_dk symbol): RC_EINVAL, and the previous kernel stays, when they
+ * fail; RC_EINVAL too when the engine has a host or curated kernel. A replaced module is unloaded only once every
+ * launch that used it has completed, so a call already enqueued on a caller's stream finishes with the old kernel. */
+int rc_engine_load_device_kernel(rc_engine *e, const char *code, size_t code_len);
+/* Up to 16 float params (h.param(i)), passed by value with every launch: they take effect from the next call, with no
+ * recompile. n_params > 16: RC_EINVAL. */
+int rc_engine_set_device_kernel_params(rc_engine *e, const float *params, uint32_t n_params);
+
 /* ---- one process, several GPUs of one node ---------------------------------------------------
  * The reference builds every channel's Stretcher in one process (src/main.rs:133-155) and one thread walks them
  * (src/stretcher_processor.rs:56-71). rc_multi is that job cut over a LIST of devices behind the same C-ABI: one
@@ -215,7 +245,7 @@ int rc_engine_resynth(rc_engine *e, uint32_t channel, uint64_t hop, const float 
  * recomputed locally, no data-path collective), and every shard's output copied ONCE, straight into its place in the
  * caller's layout (device form: hipMemcpyPeerAsync into the root device's tensor; host form: device -> the caller's
  * arrays). A host frequency kernel (rc_config::kernel) is RC_EUNSUPPORTED here: a stateful apply() sees its
- * channel's hops in order, which a cut job cannot promise; the curated device kernels work. rc_config::device is
+ * channel's hops in order, which a cut job cannot promise; the curated and user device kernels work. rc_config::device is
  * ignored. A device may be listed more than once (then its engines share it). Threading as for an engine: one thread
  * at a time per rc_multi handle; the handle owns one persistent worker thread per listed device beyond the first (created
  * by rc_multi_create, joined by rc_multi_destroy), and the calling thread's current HIP device is restored on return. */
@@ -246,6 +276,9 @@ int rc_multi_stretch_host(rc_multi *m, const float *const *in, size_t in_len, fl
  * synchronised on entry. Blocking: d_out is complete on return. */
 int rc_multi_stretch_device(rc_multi *m, uint32_t root, const float *d_in, size_t in_stride, size_t in_len,
                             float *d_out, size_t out_stride, size_t out_cap, size_t *out_len, void *hip_stream);
+/* rc_engine_load_device_kernel / _set_device_kernel_params on the engine of every listed device */
+int rc_multi_load_device_kernel(rc_multi *m, const char *code, size_t code_len);
+int rc_multi_set_device_kernel_params(rc_multi *m, const float *params, uint32_t n_params);
 
 /* ---- measurement support -------------------------------------------------------------------
  * Box calibration for bench.py (boxes of one pool differ by several per cent on the same binary): runs a fixed

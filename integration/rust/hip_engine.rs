@@ -102,6 +102,13 @@ extern "C" {
                                    hip_stream: *mut c_void) -> c_int;
     pub fn rc_calib_valu(device: c_int, hip_stream: *mut c_void, launches: u32, ms_per_launch: *mut f32,
                          ns_per_inst: *mut f32) -> c_int;
+    // user device kernels: HIP source compiled at run time (the GPU-resident hot-swapped apply())
+    pub fn rc_dk_compile(src: *const c_char, src_len: usize, code: *mut c_char, code_cap: usize, code_len: *mut usize,
+                         log: *mut c_char, log_cap: usize) -> c_int;
+    pub fn rc_engine_load_device_kernel(e: *mut RcEngine, code: *const c_char, code_len: usize) -> c_int;
+    pub fn rc_engine_set_device_kernel_params(e: *mut RcEngine, params: *const f32, n_params: u32) -> c_int;
+    pub fn rc_multi_load_device_kernel(m: *mut RcMulti, code: *const c_char, code_len: usize) -> c_int;
+    pub fn rc_multi_set_device_kernel_params(m: *mut RcMulti, params: *const f32, n_params: u32) -> c_int;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -122,6 +122,11 @@ SYMBOLS = {
     "rc_multi_stretch_device": (C.c_int, [_eng, C.c_uint32, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz,
                                           C.POINTER(_sz), C.c_void_p]),
     "rc_calib_valu": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, _fp, _fp]),
+    "rc_dk_compile": (C.c_int, [C.c_char_p, _sz, C.c_void_p, _sz, C.POINTER(_sz), C.c_void_p, _sz]),
+    "rc_engine_load_device_kernel": (C.c_int, [_eng, C.c_char_p, _sz]),
+    "rc_engine_set_device_kernel_params": (C.c_int, [_eng, _fp, C.c_uint32]),
+    "rc_multi_load_device_kernel": (C.c_int, [_eng, C.c_char_p, _sz]),
+    "rc_multi_set_device_kernel_params": (C.c_int, [_eng, _fp, C.c_uint32]),
 }
 
 _lib = None

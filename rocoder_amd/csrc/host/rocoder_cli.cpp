@@ -451,12 +451,123 @@ struct KernelStack {
     }
 };
 
+// --device-kernel-src: the same hot swap for a user DEVICE kernel (include/rocoder_hip.h, rc_dk_compile). The watcher
+// thread polls the file every 100 ms and compiles it with hiprtc (hotswapper.rs:19-30); a code object that compiled
+// waits in `pending` until the thread that drives the engine loads it between two windows (fft.rs:78: engine handles
+// are single-threaded). A failed compile prints the log and keeps the previous kernel (none on the first attempt).
+// The user-device-kernel entry points are looked up when --device-kernel-src asks for them, not linked: without the flag
+// the CLI runs over any engine library of ABI 5, also one built before they existed.
+struct DkApi {
+    decltype(&rc_dk_compile) compile = nullptr;
+    decltype(&rc_engine_load_device_kernel) load = nullptr;
+    decltype(&rc_engine_set_device_kernel_params) set_params = nullptr;
+    decltype(&rc_multi_load_device_kernel) multi_load = nullptr;
+    decltype(&rc_multi_set_device_kernel_params) multi_set_params = nullptr;
+};
+static const DkApi &dk_api() {
+    static const DkApi api = [] {
+        DkApi a;
+        a.compile = (decltype(a.compile))dlsym(RTLD_DEFAULT, "rc_dk_compile");
+        a.load = (decltype(a.load))dlsym(RTLD_DEFAULT, "rc_engine_load_device_kernel");
+        a.set_params = (decltype(a.set_params))dlsym(RTLD_DEFAULT, "rc_engine_set_device_kernel_params");
+        a.multi_load = (decltype(a.multi_load))dlsym(RTLD_DEFAULT, "rc_multi_load_device_kernel");
+        a.multi_set_params = (decltype(a.multi_set_params))dlsym(RTLD_DEFAULT, "rc_multi_set_device_kernel_params");
+        if (!a.compile || !a.load || !a.set_params || !a.multi_load || !a.multi_set_params)
+            throw std::runtime_error("--device-kernel-src: the engine library has no user device kernels");
+        return a;
+    }();
+    return api;
+}
+
+struct DeviceKernelWatcher {
+    std::mutex m;
+    std::optional<std::string> pending;
+    std::string src;
+    std::thread watcher;
+    std::atomic<bool> stop{false};
+    struct timespec last_mtime {};
+
+    void compile() {
+        std::string text;
+        if (FILE *f = fopen(src.c_str(), "rb")) {
+            char buf[4096];
+            size_t n;
+            while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
+            fclose(f);
+        } else {
+            fprintf(stderr, "WARN cannot read device kernel %s\n", src.c_str());
+            return;
+        }
+        std::string esc;
+        for (char c : src) {
+            if (c == '"' || c == '\\') esc += '\\';
+            esc += c;
+        }
+        text = "#line 1 \"" + esc + "\"\n" + text;  // diagnostics name the user's file and lines
+        std::vector<char> log(1 << 16);
+        size_t n = 0;
+        int rc = dk_api().compile(text.data(), text.size(), nullptr, 0, &n, log.data(), log.size());
+        std::string code;
+        if (rc == RC_ECAPACITY) {
+            code.resize(n);
+            rc = dk_api().compile(text.data(), text.size(), &code[0], code.size(), &n, log.data(), log.size());
+        }
+        if (rc != RC_OK) {
+            fprintf(stderr, "================ device kernel compilation failed ================\n%s\n%s\n", log.data(),
+                    rc_last_error());
+            fprintf(stderr, "WARN Failed to compile device kernel %s\n", src.c_str());
+            return;
+        }
+        std::lock_guard<std::mutex> lk(m);
+        pending = std::move(code);
+    }
+    void start(const std::string &path) {
+        src = path;
+        struct stat st;
+        if (stat(path.c_str(), &st) == 0) last_mtime = st.st_mtim;
+        compile();  // synchronous first attempt
+        watcher = std::thread([this] {
+            while (!stop.load()) {
+                std::this_thread::sleep_for(std::chrono::milliseconds(100));
+                struct stat st2;
+                if (stat(src.c_str(), &st2) == 0 && (st2.st_mtim.tv_sec != last_mtime.tv_sec ||
+                                                     st2.st_mtim.tv_nsec != last_mtime.tv_nsec)) {
+                    last_mtime = st2.st_mtim;
+                    compile();
+                }
+            }
+        });
+    }
+    // the code object compiled since the last call, if any
+    std::optional<std::string> take() {
+        std::lock_guard<std::mutex> lk(m);
+        std::optional<std::string> c = std::move(pending);
+        pending.reset();
+        return c;
+    }
+    ~DeviceKernelWatcher() {
+        stop.store(true);
+        if (watcher.joinable()) watcher.join();
+    }
+};
+
 static bool g_timing = false;  // ROCODER_CLI_TIMING
 
 // ------------------------------------------------------------------ src/stretcher.rs over the engine
 struct Engine {
     rc_engine *h = nullptr;
     std::mutex m;  // one thread at a time per handle
+    DeviceKernelWatcher *dk = nullptr;  // --device-kernel-src
+    // between two windows, with m held: a device kernel the watcher compiled since the last window
+    void poll_device_kernel() {
+        if (!dk) return;
+        if (auto code = dk->take()) {
+            if (dk_api().load(h, code->data(), code->size()) == RC_OK)
+                fprintf(stderr, "INFO Got new device kernel\n");
+            else
+                fprintf(stderr, "WARN loading the device kernel failed: %s\n", rc_last_error());
+        }
+    }
     ~Engine() { rc_engine_destroy(h); }
 };
 struct Stretcher {
@@ -480,6 +591,7 @@ struct Stretcher {
             int rc;
             {
                 std::lock_guard<std::mutex> lk(eng->m);
+                eng->poll_device_kernel();
                 rc = rc_engine_next_window(eng->h, channel, out.data(), out.size(), &n);
             }
             if (rc == RC_OK) {
@@ -648,6 +760,8 @@ struct Opt {  // src/main.rs:27-122
     bool rotate_channels = false;
     std::optional<std::string> freq_kernel;
     std::optional<std::string> device_kernel;  // not in the reference: curated on-GPU kernels
+    std::optional<std::string> device_kernel_src;  // not in the reference: a user kernel in HIP, hot-swapped
+    std::vector<float> dk_params;
     int kernel_threads = 0;
     uint64_t fade_ms = 1000;
     std::optional<uint64_t> start_ms, duration_ms;
@@ -673,6 +787,9 @@ void usage() {
             "    -s, --start <start>                Start time in input audio (hh:mm:ss.ss)\n"
             "    -w, --window <window-len>          Processing window size [default: 16384]\n"
             "        --device-kernel <spec>         On-GPU frequency kernel: gain:<g> | band:<lo>:<hi>:<g_in>:<g_out> | shift:<bins>\n"
+            "        --device-kernel-src <file.hip> On-GPU frequency kernel in HIP, recompiled when the file changes: defines\n"
+            "                                       __device__ float2 rc_apply(const rc_spectrum &X, uint32_t j, const rc_hop &h)\n"
+            "        --dk-params <a,b,...>          Up to 16 floats for --device-kernel-src (h.param(i))\n"
             "        --kernel-threads <n>           Host threads calling --freq-kernel (channels in parallel; needs a re-entrant kernel)\n"
             "        --seed <u64>                   Phase-source seed (the reference uses an unseeded thread_rng)\n"
             "        --device <n>                   HIP device ordinal [default: 0]\n"
@@ -719,6 +836,20 @@ int run(int argc, char **argv) {
         else if (a == "--rotate-channels") o.rotate_channels = true;
         else if (a == "--freq-kernel") o.freq_kernel = need(i);
         else if (a == "--device-kernel") o.device_kernel = need(i);
+        else if (a == "--device-kernel-src") o.device_kernel_src = need(i);
+        else if (a == "--dk-params") {
+            const std::string v = need(i);
+            for (size_t b = 0; b <= v.size();) {
+                const size_t c = std::min(v.find(',', b), v.size());
+                char *end = nullptr;
+                const std::string t = v.substr(b, c - b);
+                const float x = strtof(t.c_str(), &end);
+                if (t.empty() || *end) throw std::runtime_error("bad --dk-params " + v);
+                o.dk_params.push_back(x);
+                b = c + 1;
+            }
+            if (o.dk_params.size() > 16) throw std::runtime_error("--dk-params takes at most 16 values");
+        }
         else if (a == "--kernel-threads") o.kernel_threads = atoi(need(i).c_str());
         else if (a == "-x" || a == "--fade") o.fade_ms = dur(need(i));
         else if (a == "-s" || a == "--start") o.start_ms = dur(need(i));
@@ -740,6 +871,9 @@ int run(int argc, char **argv) {
     if (!o.input) throw std::runtime_error("recording from an input device (no -i) is not supported: pass -i <file.wav> or -i -");
     if (!o.output) throw std::runtime_error("live playback (no -o) is not supported: pass -o <file.wav>");
     if (o.pitch_multiple < -128 || o.pitch_multiple > 127) throw std::runtime_error("pitch_multiple must fit an i8");
+    if (o.device_kernel_src && (o.freq_kernel || o.device_kernel))
+        throw std::runtime_error("--device-kernel-src cannot be combined with --freq-kernel or --device-kernel");
+    if (!o.dk_params.empty() && !o.device_kernel_src) throw std::runtime_error("--dk-params needs --device-kernel-src");
 
     // ROCODER_CLI_TIMING=1: wall time of each phase on stderr (dev aid)
     const bool timing = g_timing = getenv("ROCODER_CLI_TIMING") != nullptr;
@@ -763,6 +897,11 @@ int run(int argc, char **argv) {
 
     KernelStack kernels;
     if (o.freq_kernel) kernels.start(*o.freq_kernel);
+    DeviceKernelWatcher dk;
+    if (o.device_kernel_src) {
+        dk_api();  // (fails here, before any work, when the library lacks them)
+        dk.start(*o.device_kernel_src);
+    }
 
     rc_config cfg{};
     cfg.struct_size = sizeof cfg;
@@ -810,6 +949,15 @@ int run(int argc, char **argv) {
         rc_multi *m = nullptr;
         if (rc_multi_create(&cfg, o.devices.data(), (uint32_t)o.devices.size(), &m) != RC_OK)
             throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+        if (o.device_kernel_src) {  // (one call computes the whole job: the kernel compiled by now is the one it runs)
+            if (auto code = dk.take())
+                if (dk_api().multi_load(m, code->data(), code->size()) != RC_OK ||
+                    dk_api().multi_set_params(m, o.dk_params.data(), (uint32_t)o.dk_params.size()) != RC_OK) {
+                    const std::string err = rc_last_error();
+                    rc_multi_destroy(m);
+                    throw std::runtime_error("rocoder_hip: " + err);
+                }
+        }
         lap("engine create");
         const size_t in_len = audio.data[0].size(), cap = rc_offline_output_len(&cfg, in_len);
         Audio out;
@@ -833,6 +981,12 @@ int run(int argc, char **argv) {
     }
     auto eng = std::make_shared<Engine>();
     if (rc_engine_create(&cfg, &eng->h) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+    if (o.device_kernel_src) {
+        if (dk_api().set_params(eng->h, o.dk_params.data(), (uint32_t)o.dk_params.size()) != RC_OK)
+            throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+        eng->dk = &dk;
+        eng->poll_device_kernel();  // the first attempt's kernel, before the first window
+    }
     lap("engine create");
 
     // one Stretcher per channel, fed the whole channel as one chunk (src/main.rs:133-153)

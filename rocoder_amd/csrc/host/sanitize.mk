@@ -12,22 +12,23 @@ all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../b
 	mkdir -p ../../bin
 	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(COMMON) -o $@ -L../.. -lrocoder_hip \
 	    -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath-link,/opt/rocm/lib
-../../bin/libstub_engine.so: $(ROOT)/tests/c/stub_engine.c $(ROOT)/include/rocoder_hip.h
+../../bin/libstub_engine.so: $(ROOT)/tests/c/stub_engine.c $(ROOT)/tests/c/stub_engine_dk.c $(ROOT)/include/rocoder_hip.h
 	mkdir -p ../../bin
-	gcc -g -O1 -fPIC -shared -fsanitize=thread -I$(ROOT)/include -o $@ $(ROOT)/tests/c/stub_engine.c
+	gcc -g -O1 -fPIC -shared -fsanitize=thread -I$(ROOT)/include -o $@ $(ROOT)/tests/c/stub_engine.c $(ROOT)/tests/c/stub_engine_dk.c
 ../../bin/rocoder_tsan: rocoder_cli.cpp $(ROOT)/include/rocoder_hip.h ../../bin/libstub_engine.so
 	$(CXX) -fsanitize=thread $(COMMON) -o $@ -L../../bin -lstub_engine -Wl,-rpath,'$$ORIGIN'
 # The ENGINE's host code (rc_engine.cpp: worker pools, the pinned three-set pipeline, rc_multi's persistent workers, the
 # streaming seam) host-only over tests/c/hip_stub.cpp - a HIP runtime whose device memory is host memory and whose
 # kernels compute nothing - driven by tests/c/engine_host_driver.cpp:
 #   ../../bin/engine_asan : -fsanitize=address,undefined      ../../bin/engine_tsan : -fsanitize=thread
-ENGINE_SRC := ../rc_engine.cpp $(ROOT)/tests/c/hip_stub.cpp $(ROOT)/tests/c/hip_stub_long.cpp $(ROOT)/tests/c/engine_host_driver.cpp
+ENGINE_SRC := ../rc_engine.cpp ../rc_rtc.cpp $(ROOT)/tests/c/hip_stub.cpp $(ROOT)/tests/c/hip_stub_long.cpp \
+    $(ROOT)/tests/c/hip_stub_rtc.cpp $(ROOT)/tests/c/engine_host_driver.cpp
 ENGINE_FLAGS := -g -O1 -std=c++17 -Wall -Wno-unused-function -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -DRC_PMAX=32 \
     -I/opt/rocm/include -x c++
-../../bin/engine_asan: $(ENGINE_SRC) ../rc_kernels.h ../rc_long.h $(ROOT)/include/rocoder_hip.h
+../../bin/engine_asan: $(ENGINE_SRC) ../rc_kernels.h ../rc_long.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
 	mkdir -p ../../bin
-	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(ENGINE_FLAGS) $(ENGINE_SRC) -o $@ -lpthread
-../../bin/engine_tsan: $(ENGINE_SRC) ../rc_kernels.h ../rc_long.h $(ROOT)/include/rocoder_hip.h
+	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(ENGINE_FLAGS) $(ENGINE_SRC) -o $@ -lpthread -ldl
+../../bin/engine_tsan: $(ENGINE_SRC) ../rc_kernels.h ../rc_long.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
 	mkdir -p ../../bin
-	$(CXX) -fsanitize=thread $(ENGINE_FLAGS) $(ENGINE_SRC) -o $@ -lpthread
+	$(CXX) -fsanitize=thread $(ENGINE_FLAGS) $(ENGINE_SRC) -o $@ -lpthread -ldl
 .PHONY: all

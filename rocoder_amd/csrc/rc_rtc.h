@@ -1,0 +1,47 @@
+// User device kernels compiled at run time (include/rocoder_hip.h: rc_dk_compile, rc_engine_load_device_kernel): the
+// hiprtc compile of prelude + user source + wrapper (rc_user_dk_prelude.hpp, rc_user_dk_wrapper.hpp), the check of a
+// code object before it reaches the HIP runtime, and the hipModule* calls. rc_engine.cpp calls only these functions.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+namespace rc {
+
+constexpr uint32_t DK_MAX_PARAMS = 16;
+
+// Host mirror of the prelude's rc_dk_args (the wrapper kernel's one argument): keep the two in step
+struct UserDkArgs {
+    const float2 *in;
+    float2 *out;
+    uint64_t row_first;
+    int64_t hop_first;
+    uint64_t hop_count;
+    uint64_t time_ms;
+    uint32_t n, mask;
+    uint32_t ch_first, n_params;
+    float params[DK_MAX_PARAMS];
+};
+static_assert(sizeof(UserDkArgs) == 128, "rc_dk_args layout");
+
+// Every function returns an RC_* status and, on failure, a one-line reason in *why.
+
+// hiprtc: source -> gfx950 code object in *code. RC_OK; RC_EINVAL with the compiler log in *log when the source does
+// not compile or defines no rc_apply (*why: the log's first error line); RC_EUNSUPPORTED when hiprtc cannot be loaded.
+// Pure host, thread-safe.
+int rtc_compile(const char *src, size_t src_len, std::string *code, std::string *log, std::string *why);
+
+// RC_OK when `code` is an ELF64 AMDGPU code object for gfx950 that defines the symbol rc_user_dk, else RC_EINVAL.
+// Reads nothing outside [code, code + len).
+int rtc_check_code_object(const void *code, size_t len, std::string *why);
+
+struct UserModule;
+// hipModuleLoadData + hipModuleGetFunction("rc_user_dk") on the current device (RC_EHIP on failure)
+int rtc_load(const void *code, size_t len, UserModule **out, std::string *why);
+void rtc_unload(UserModule *m);
+// rows = hop spectra of a.n bins; a.row_first is set per launch (rows are chunked below the grid.y limit)
+hipError_t rtc_launch(const UserModule *m, UserDkArgs a, uint64_t rows, hipStream_t s);
+
+}  // namespace rc

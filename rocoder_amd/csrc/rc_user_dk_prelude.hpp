@@ -1,0 +1,55 @@
+// The prelude of a user device kernel (rc_dk_compile): hiprtc compiles it, then the user's source, then
+// rc_user_dk_wrapper.hpp, as one translation unit for gfx950. rc_rtc.cpp embeds both files as text; the raw string
+// below is the whole of what the user's code sees.
+//
+// The user writes one function,
+//   __device__ float2 rc_apply(const rc_spectrum &X, uint32_t j, const rc_hop &h);   // returns Y[j]
+// X is one hop's N-bin spectrum in natural DFT order; every index is reduced modulo N, so no read leaves the hop, and
+// the user gets no pointer to write through. rc_apply must terminate: the engine cannot preempt a kernel.
+R"rc_prelude(
+typedef __hip_internal::uint32_t uint32_t;
+typedef __hip_internal::int32_t int32_t;
+typedef __hip_internal::uint64_t uint64_t;
+typedef __hip_internal::int64_t int64_t;
+
+#define RC_DK_MAX_PARAMS 16u
+
+// kernel argument block; the host mirror is rc::UserDkArgs (rc_rtc.h)
+struct rc_dk_args {
+    const float2 *in;    // [rows][n]
+    float2 *out;         // [rows][n], never aliases `in`
+    uint64_t row_first;  // first row of this launch (grid.y chunks)
+    int64_t hop_first;   // row r is hop hop_first + r % hop_count of channel ch_first + r / hop_count
+    uint64_t hop_count;
+    uint64_t time_ms;
+    uint32_t n, mask;    // mask = n - 1 for powers of two, else 0
+    uint32_t ch_first, n_params;
+    float params[RC_DK_MAX_PARAMS];
+};
+
+// One hop's spectrum, read-only. X[i] is X[i mod n] for any i.
+struct rc_spectrum {
+    const float2 *p_;
+    uint32_t n;
+    uint32_t mask_;
+    __device__ float2 operator[](int64_t i) const {
+        if (mask_) return p_[(uint64_t)i & mask_];  // powers of two: two's complement makes this i mod n
+        if ((uint64_t)i < n) return p_[i];
+        int64_t r = i % (int64_t)n;
+        if (r < 0) r += n;
+        return p_[r];
+    }
+};
+
+// What the hop is: window length, channel, hop index k (the k of rc_phase_key), the launch's time and the params.
+// time_ms is one value per launch (rc_config::kernel_time_ms, or the wall clock when the launch was enqueued).
+struct rc_hop {
+    uint32_t n;
+    uint32_t channel;
+    uint64_t hop;
+    uint64_t time_ms;
+    uint32_t n_params;
+    const float *params_;
+    __device__ float param(uint32_t i) const { return i < n_params ? params_[i] : 0.f; }
+};
+)rc_prelude"

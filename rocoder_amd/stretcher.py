@@ -67,6 +67,39 @@ def load_kernel_library(path: str):
     return k
 
 
+class DeviceKernelCompileError(RocoderError):
+    """A user device kernel that does not compile: `log` holds the compiler's output."""
+
+    def __init__(self, code: int, msg: str, log: str):
+        super().__init__(code, msg + ("\n" + log if log else ""))
+        self.log = log
+
+
+def compile_device_kernel(src, name: Optional[str] = None) -> bytes:
+    """HIP source defining `__device__ float2 rc_apply(const rc_spectrum &X, uint32_t j, const rc_hop &h)` -> gfx950
+    code object (rc_dk_compile; pure host, no device). `name` is the file name diagnostics give (default
+    rc_user_dk.hip). Raises DeviceKernelCompileError carrying the compiler log."""
+    L = _lib.lib()
+    text = src.encode() if isinstance(src, str) else bytes(src)
+    if name is not None:
+        text = f'#line 1 "{name}"\n'.encode() + text
+    n = C.c_size_t(0)
+    log = C.create_string_buffer(1 << 16)
+    rc = L.rc_dk_compile(text, len(text), None, 0, C.byref(n), log, len(log))
+    if rc == _lib.RC_ECAPACITY:
+        code = C.create_string_buffer(n.value)
+        rc = L.rc_dk_compile(text, len(text), code, n.value, C.byref(n), log, len(log))
+        if rc == _lib.RC_OK:
+            return code.raw[:n.value]
+    raise DeviceKernelCompileError(rc, L.rc_last_error().decode(errors="replace"),
+                                   log.value.decode(errors="replace"))
+
+
+def _params_array(params):
+    vals = [float(v) for v in params]
+    return (C.c_float * max(1, len(vals)))(*vals), len(vals)
+
+
 def make_config(window_len=16384, factor=1.0, amplitude=1.0, pitch_multiple=1, sample_rate=44100,
                 channels=1, buffer_secs=1.0, seed=0, device=0, window=None, kernel=None,
                 kernel_time_ms=0, max_batch_hops=0, kernel_threads=0, device_kernel=None):
@@ -348,6 +381,20 @@ class Engine:
         self._check(self._L.rc_engine_resynth(self._h, channel, hop, _fp(s), _fp(out)))
         return out
 
+    # ---- user device kernel (rc_engine_load_device_kernel)
+    def load_device_kernel(self, code: Optional[bytes]):
+        """Load a code object from compile_device_kernel (None: remove the kernel); it runs from the next call."""
+        self._check(self._L.rc_engine_load_device_kernel(self._h, code, 0 if code is None else len(code)))
+
+    def set_device_kernel_source(self, src, name: Optional[str] = None):
+        """compile_device_kernel + load_device_kernel."""
+        self.load_device_kernel(compile_device_kernel(src, name))
+
+    def set_device_kernel_params(self, params: Sequence[float]):
+        """Up to 16 floats, h.param(i) in the kernel; they take effect from the next call."""
+        arr, n = _params_array(params)
+        self._check(self._L.rc_engine_set_device_kernel_params(self._h, arr, n))
+
 
 
 class MultiEngine:
@@ -401,6 +448,17 @@ class MultiEngine:
         self._check(self._L.rc_multi_stretch_host(self._h, ins, x.shape[1], outs, out.shape[1], C.byref(got)))
         assert got.value == n_out
         return out[:, :n_out]
+
+    def load_device_kernel(self, code: Optional[bytes]):
+        """The code object on every listed device's engine (None: remove the kernel)."""
+        self._check(self._L.rc_multi_load_device_kernel(self._h, code, 0 if code is None else len(code)))
+
+    def set_device_kernel_source(self, src, name: Optional[str] = None):
+        self.load_device_kernel(compile_device_kernel(src, name))
+
+    def set_device_kernel_params(self, params: Sequence[float]):
+        arr, n = _params_array(params)
+        self._check(self._L.rc_multi_set_device_kernel_params(self._h, arr, n))
 
     def set_staging(self, force: bool):
         """Diagnostic (rc_multi_set_staging): shares on the root's own device take the copy path of a remote one."""
@@ -601,15 +659,21 @@ class StretcherProcessor:
 
 def stretch(channels_in, window_len=16384, factor=1.0, amplitude=1.0, pitch_multiple=1, seed=0,
             sample_rate=44100, kernel=None, device=0, kernel_time_ms=0, kernel_threads=0,
-            device_kernel=None) -> np.ndarray:
-    """Offline `-o` run (src/main.rs:124-160 minus file I/O): host [C, L] -> host [C, n_out]."""
+            device_kernel=None, device_kernel_source=None, device_kernel_params=None) -> np.ndarray:
+    """Offline `-o` run (src/main.rs:124-160 minus file I/O): host [C, L] -> host [C, n_out].
+    device_kernel_source: HIP source of a user device kernel (compile_device_kernel), with device_kernel_params."""
     x = np.ascontiguousarray(np.atleast_2d(channels_in), dtype=np.float32)
     with Engine(window_len=window_len, factor=factor, amplitude=amplitude,
                 pitch_multiple=pitch_multiple, sample_rate=sample_rate, channels=x.shape[0],
                 seed=seed, device=device, kernel=kernel, kernel_time_ms=kernel_time_ms,
                 kernel_threads=kernel_threads, device_kernel=device_kernel) as e:
+        if device_kernel_source is not None:
+            e.set_device_kernel_source(device_kernel_source)
+        if device_kernel_params is not None:
+            e.set_device_kernel_params(device_kernel_params)
         return e.stretch_host(x)
 
 
 __all__ = ["AudioSpec", "AudioBus", "Engine", "ReFFT", "Stretcher", "StretcherProcessor", "stretch",
-           "derive_params", "offline_output_len", "load_kernel_library", "RocoderError"]
+           "derive_params", "offline_output_len", "load_kernel_library", "RocoderError", "compile_device_kernel",
+           "DeviceKernelCompileError"]
