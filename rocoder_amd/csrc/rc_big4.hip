@@ -21,34 +21,7 @@ namespace {
 // addresses) may still be in flight when the next hop starts
 #define BIG4_BAR()                                                                       \
     do {                                                                                 \
-        if (RC_B4_ABL & 16) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           \
-        else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");           \
-    } while (0)
-#ifndef RC_B4_ABL
-#define RC_B4_ABL 0  // timing-only ablations (`make variant`; results are wrong by construction): 1 no input loads,
-                     // 4 no output stores, 8 the E2 and E3 barriers become fences (32: E2 only, 64: E3 only),
-                     // 128 the entry barriers of E1 / E4 become fences, 16 no barrier at all - profiles/r04a_c5_ablations.txt
-#endif
-// (timing-only, RC_B4_ABL bit 8: the E2 / E3 barriers become compiler fences - what desynchronised waves would buy)
-#define BIG4_BAR_MID()                                                          \
-    do {                                                                        \
-        if (RC_B4_ABL & 8) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-        else BIG4_BAR();                                                        \
-    } while (0)
-#define BIG4_BAR_ENTRY()  /* (bit 128: the entry barriers of E1 / E4 - what hop4's own-region scheme would drop) */ \
-    do {                                                                        \
-        if (RC_B4_ABL & 128) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-        else BIG4_BAR();                                                        \
-    } while (0)
-#define BIG4_BAR_E2()                                                           \
-    do {                                                                        \
-        if (RC_B4_ABL & 32) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  \
-        else BIG4_BAR_MID();                                                    \
-    } while (0)
-#define BIG4_BAR_E3()                                                           \
-    do {                                                                        \
-        if (RC_B4_ABL & 64) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  \
-        else BIG4_BAR_MID();                                                    \
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                 \
     } while (0)
 // R = 64 (BASELINE C5): what the measurements of rounds 2-4 settled (docs/LAB_NOTES, DESIGN.md 5.4, profiles/r04a_c5_ablations.txt)
 //  * the last inverse stage (the one that pairs head sample q with tail sample q + PH) is computed inside the
@@ -159,15 +132,11 @@ __global__ __launch_bounds__(BIG4_T, 2) void big4_kernel(const HopParams p) {
                 constexpr int PB = BIG4_PIPE_ROWS, NB = R / PB;
                 float xp0[2][PB], xp1[2][PB];
                 auto issue = [&](int i, float (&x0)[PB], float (&x1)[PB]) {
+                    (void)k;  // (the closure's reference to k keeps this kernel's measured instruction schedule)
 #pragma unroll
                     for (int q = 0; q < PB; ++q) {
-                        if (RC_B4_ABL & 1) {
-                            x0[q] = (float)(lane2 + ROW(i * PB + q)) + (float)k;
-                            x1[q] = x0[q] * 0.5f;
-                        } else {
-                            x0[q] = (src + 2 * T * ROW(i * PB + q))[lane2];
-                            x1[q] = (src + 2 * T * ROW(i * PB + q))[lane2 + 1];
-                        }
+                        x0[q] = (src + 2 * T * ROW(i * PB + q))[lane2];
+                        x1[q] = (src + 2 * T * ROW(i * PB + q))[lane2 + 1];
                     }
                 };
                 issue(0, xp0[0], xp1[0]);
@@ -199,13 +168,8 @@ __global__ __launch_bounds__(BIG4_T, 2) void big4_kernel(const HopParams p) {
                 float xr0[LB], xr1[LB], wr0[HANN ? 1 : LB], wr1[HANN ? 1 : LB];
 #pragma unroll
                 for (int q = 0; q < LB; ++q) {
-                    if (RC_B4_ABL & 1) {  // timing only: no input loads
-                        xr0[q] = (float)(lane2 + ROW(q0 + q)) + (float)k;
-                        xr1[q] = xr0[q] * 0.5f;
-                    } else {
-                        xr0[q] = (src + 2 * T * ROW(q0 + q))[lane2];
-                        xr1[q] = (src + 2 * T * ROW(q0 + q))[lane2 + 1];
-                    }
+                    xr0[q] = (src + 2 * T * ROW(q0 + q))[lane2];
+                    xr1[q] = (src + 2 * T * ROW(q0 + q))[lane2 + 1];
                     if constexpr (!HANN) {
                         wr0[q] = (win + 2 * T * ROW(q0 + q))[lane2];
                         wr1[q] = (win + 2 * T * ROW(q0 + q))[lane2 + 1];
@@ -247,7 +211,7 @@ __global__ __launch_bounds__(BIG4_T, 2) void big4_kernel(const HopParams p) {
                 // R = 64, two rounds: the LDS takes the 32 stores of a wave at ~50 cycles apiece while all eight waves
                 // store (80 B/clk per CU), so the second round's stores are issued one at a time between the butterflies
                 // of F2 on the first round's group instead of in front of a barrier
-                BIG4_BAR_ENTRY();
+                BIG4_BAR();
 #pragma unroll
                 for (int q = 0; q < 32; ++q) lds[b1s + q] = to_f2(v[q]);
                 BIG4_BAR();
@@ -326,13 +290,13 @@ __global__ __launch_bounds__(BIG4_T, 2) void big4_kernel(const HopParams p) {
             const int b2s = lf | (uu << 10);
 #pragma unroll
             for (int rnd = 0; rnd < G; ++rnd) {
-                BIG4_BAR_E2();
+                BIG4_BAR();
 #pragma unroll
                 for (int kk = 0; kk < 32; ++kk) {
                     if (R == 32) lds[b2s + (kk << 5)] = to_f2(w[kk]);
                     else lds[b2s + ((kk >> 4) << 5) + ((kk & 15) << 6)] = to_f2(w[32 * (kk >> 4) + 16 * rnd + (kk & 15)]);
                 }
-                BIG4_BAR_E2();
+                BIG4_BAR();
 #pragma unroll
                 for (int s = 0; s < NS; ++s) {
                     if (R == 64 && ((s & 1) != rnd)) continue;
@@ -438,7 +402,7 @@ __global__ __launch_bounds__(BIG4_T, 2) void big4_kernel(const HopParams p) {
             const int tid = ptid(), l4 = tid & 15, hi = tid >> 4;
 #pragma unroll
             for (int rnd = 0; rnd < G; ++rnd) {
-                BIG4_BAR_E3();
+                BIG4_BAR();
 #pragma unroll
                 for (int s = 0; s < NS; ++s) {
                     if (R == 64 && ((s & 1) != rnd)) continue;
@@ -451,7 +415,7 @@ __global__ __launch_bounds__(BIG4_T, 2) void big4_kernel(const HopParams p) {
 #pragma unroll
                     for (int q = 0; q < 16; ++q) lds[base + q] = to_f2(st[s][q]);
                 }
-                BIG4_BAR_E3();
+                BIG4_BAR();
 #pragma unroll
                 for (int kk = 0; kk < 32; ++kk) {
                     // R = 32: register kk = P4..P8; R = 64: kk = (group g = P14) << 4 | (P5..P8), P4 = rnd
@@ -480,7 +444,7 @@ __global__ __launch_bounds__(BIG4_T, 2) void big4_kernel(const HopParams p) {
 #pragma unroll
                 for (int j = 0; j < 32; ++j) v[j] = grp[j];
             }
-            BIG4_BAR_ENTRY();
+            BIG4_BAR();
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < 32; ++j) lds[b4s + (j << 4)] = to_f2(v[j]);
@@ -641,7 +605,6 @@ __global__ __launch_bounds__(BIG4_T, 2) void big4_kernel(const HopParams p) {
                         // stretcher.rs:97-100; with the computed envelope the amplitude is already inside it
                         const v2f o = HANN ? (head + tq[q]) * v2f{e0[q], e1[q]} : (head + tq[q]) * v2f{e0[q], e1[q]} * ampk;
                         if constexpr (PITCH1) {
-                            if (!(RC_B4_ABL & 4) || o.x == 1.2345f)  // (bit 4, timing only: no output stores)
                             __builtin_nontemporal_store(o, (GV2W)(dst + 2 * T * (q0 + q) + lane2));
                         } else {
                             const uint32_t a0 = kr + 2u * (uint32_t)(tid + T * (q0 + q)), a1 = a0 + 1;

@@ -45,11 +45,6 @@ constexpr int clog2(int v) { return v <= 1 ? 0 : 1 + clog2(v >> 1); }
 
 // points per thread for the large windows (tunable: 32 -> 256 threads, 2 waves/SIMD, 3 passes;
 // 16 -> 512 threads, 4 waves/SIMD, 4 passes)
-// Timing-only diagnostic builds (results are wrong): bit 0 = no phase hash/sincos, bit 1 = no global
-// loads/stores, bit 2 = no LDS exchanges/barriers, bit 3 = no butterflies, bit 4 = no middle stage.
-#ifndef RC_LOADCH
-#define RC_LOADCH 32
-#endif
 #ifndef RC_PMAX
 #define RC_PMAX 32
 #endif
@@ -89,9 +84,6 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
 // butterfly whenever its SIMD partner is waiting on LDS / memory. The butterflies are written as
 // plain ext-vector code: hipcc selects v_pk_fma/mul/add with op_sel, neg and SGPR/inline constants
 // by itself, so there are no inline-asm boundary pads and the scheduler is free.
-#ifndef RC_PK
-#define RC_PK 1
-#endif
 __device__ __forceinline__ v2f to_v(float2 a) {
     v2f r;
     r.x = a.x;
@@ -132,9 +124,6 @@ __device__ __forceinline__ void opaque(int &x) { asm volatile("" : "+v"(x)); }
 // per phase id, written to the debug buffer passed in HopParams::spec.
 #ifndef RC_STAMP
 #define RC_STAMP 0
-#endif
-#ifndef RC_SWP
-#define RC_SWP 2
 #endif
 struct Stamps {
 #if RC_STAMP
@@ -192,25 +181,25 @@ __device__ __forceinline__ uint32_t phase_hash_x(uint32_t x) {
     return x;
 }
 __device__ __forceinline__ float phase_rev_lower(uint32_t h) { return __uint_as_float(0x3F000000u | (h >> 9)); }
-#ifndef RC_MAD16
-#define RC_MAD16 1
-#endif
+// MAD16: (h & 0xFFFF) * 128 + 0x3F000000 in one instruction: v_mad_u32_u16 multiplies the LOW HALVES of its first two
+// operands (no mask, no shift), the addend is the inline constant 0.5; the fields do not overlap, so + is |
+// (-1.2 % on hop4_kernel; the wave-local kernels of rc_hopw.hip take the mask-and-shift form, see there)
+template <bool MAD16 = true>
 __device__ __forceinline__ float phase_rev_upper(uint32_t h) {
-#if RC_MAD16
-    // (h & 0xFFFF) * 128 + 0x3F000000 in one instruction: v_mad_u32_u16 multiplies the LOW HALVES of its first two
-    // operands (no mask, no shift), the addend is the inline constant 0.5; the fields do not overlap, so + is |
-    uint32_t r;
-    asm("v_mad_u32_u16 %0, %1, %2, 0.5" : "=v"(r) : "v"(h), "s"(128u));
-    return __uint_as_float(r);
-#else
-    return __uint_as_float(0x3F000000u | ((h & 0xFFFFu) << 7));
-#endif
+    if constexpr (MAD16) {
+        uint32_t r;
+        asm("v_mad_u32_u16 %0, %1, %2, 0.5" : "=v"(r) : "v"(h), "s"(128u));
+        return __uint_as_float(r);
+    } else {
+        return __uint_as_float(0x3F000000u | ((h & 0xFFFFu) << 7));
+    }
 }
 // counter x = c * mul + k0 of c < M: (-cos, -sin) of bin c (lo*) and of bin c + M (up*)
+template <bool MAD16 = true>
 __device__ __forceinline__ void phase_ncs2_x(uint32_t x, float &lo_nc, float &lo_ns, float &up_nc,
                                              float &up_ns) {
     const uint32_t h = phase_hash_x(x);
-    const float fl = phase_rev_lower(h), fu = phase_rev_upper(h);
+    const float fl = phase_rev_lower(h), fu = phase_rev_upper<MAD16>(h);
     lo_nc = __builtin_amdgcn_cosf(fl);
     lo_ns = __builtin_amdgcn_sinf(fl);
     up_nc = __builtin_amdgcn_cosf(fu);

@@ -22,11 +22,7 @@ __device__ __forceinline__ v2f vcmul(v2f a, v2f k) {  // a * k
 }
 // a * a: with a runtime operand hipcc builds (-a.y, a.x) with a v_xor + v_mov in front of the FMA; as VOP3P source
 // modifiers (op_sel + neg_lo) the square is two instructions instead of four
-#ifndef RC_VCSQ
-#define RC_VCSQ 1
-#endif
 __device__ __forceinline__ v2f vcsq(v2f a) {
-    if (!RC_VCSQ) return vcmul(a, a);
     const v2f t = __builtin_shufflevector(a, a, 0, 0) * a;
     v2f r;  // t + a.yy * (-a.y, a.x)
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]" : "=v"(r) : "v"(a), "v"(a), "v"(t));
@@ -36,14 +32,6 @@ __device__ __forceinline__ v2f vcsq(v2f a) {
 // DIT stages S_LO..S_HI on NREG registers: register bit (s - REG_LO) <-> position bit s; the
 // position bits below REG_LO are the runtime value l (< 2^REG_LO; HAS_L = false means l == 0).
 //   a' = a + w b, b' = a - w b, w = exp(-2 pi i (p mod 2^s) / 2^(s+1))   (conjugated when CONJ)
-// butterfly with the twiddle w' = -i w (the second half of a stage's twiddles is the first half
-// rotated by -i): alpha = w.y, beta = -w.x, so only w2r = w.xx * (-sgn) is needed, no complex product
-__device__ __forceinline__ void vdit_rot(v2f a, v2f b, v2f w, v2f w2r, v2f &r, v2f &o) {
-    const v2f t = __builtin_elementwise_fma(b, __builtin_shufflevector(w, w, 1, 1), a);
-    r = __builtin_elementwise_fma(__builtin_shufflevector(b, b, 1, 0), w2r, t);
-    const v2f two = {2.0f, 2.0f};
-    o = __builtin_elementwise_fma(a, two, -r);
-}
 
 // wfine = W_{2^(S_HI+1)}^l, the base twiddle of the last stage; the base of stage s - 1 is the
 // square of the base of stage s (no table loads inside the hop loop: a global load waited on in
@@ -52,9 +40,6 @@ __device__ __forceinline__ v2f xld(const float2 *lds, int idx) { return to_v(lds
 // Runtime-twiddle butterflies with the (-w.y, w.y) / (w.x, -w.x) operand expressed as VOP3P source
 // modifiers (op_sel + neg_lo / neg_hi): hipcc does not fold a per-lane negation into the modifiers, so
 // the plain-C++ form needs one v_pk_mul per twiddle and form (124 per hop) to build those operands.
-#ifndef RC_ASMNEG
-#define RC_ASMNEG 1
-#endif
 //   r = a + w b (CONJ: a + conj(w) b), o = 2a - r
 template <bool CONJ>
 __device__ __forceinline__ void vdit_m(v2f a, v2f b, v2f w, v2f &r, v2f &o) {
@@ -74,9 +59,6 @@ __device__ __forceinline__ void vdit_rot_m(v2f a, v2f b, v2f w, v2f &r, v2f &o) 
     o = __builtin_elementwise_fma(a, two, -r);
 }
 //   twiddle -i (CONJ: +i): no multiply at all - the swap and the sign ride on the VOP3P modifiers of two packed adds
-#ifndef RC_ASMROT
-#define RC_ASMROT 1
-#endif
 template <bool CONJ>
 __device__ __forceinline__ void vdit_i(v2f a, v2f b, v2f &r, v2f &o) {
     v2f p, m;  // p = (a.x + b.y, a.y - b.x) = a - i b ; m = (a.x - b.y, a.y + b.x) = a + i b
@@ -89,9 +71,6 @@ __device__ __forceinline__ void vdit_i(v2f a, v2f b, v2f &r, v2f &o) {
 // v_pk_fma_f32 is followed by its consumer (hipcc pads every such pair around an inline asm with an s_nop, and a
 // dependent packed FMA issues 8 cycles after its producer: a lone wave runs the one-butterfly form at half rate).
 // In place: r lands in b's registers, o in a's; ROT0 / ROT1: that butterfly's twiddle is -i w (CONJ: +i conj w).
-#ifndef RC_BF2
-#define RC_BF2 1
-#endif
 #define RC_BF_T_N "op_sel_hi:[1,0,1]"
 #define RC_BF_T_R "op_sel:[0,1,0] op_sel_hi:[1,1,1]"
 #define RC_BF_R_N "op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0]"
@@ -147,12 +126,8 @@ __device__ __forceinline__ void dit_stages(v2f (&v)[NREG], v2f wfine = v2f{1.0f,
                 if (c == 0) {
                     v[q0] = a + b;
                     v[q1] = a - b;
-                } else if (kidx == 8 && RC_ASMROT) {  // w b = -i b (forward) / +i b (inverse)
+                } else if (kidx == 8) {  // w b = -i b (forward) / +i b (inverse)
                     vdit_i<CONJ>(a, b, v[q0], v[q1]);
-                } else if (kidx == 8) {  // ... = -(b.yx * sgn)
-                    const v2f ib = __builtin_shufflevector(b, b, 1, 0) * sgn;
-                    v[q0] = a - ib;
-                    v[q1] = a + ib;
                 } else {
                     const v2f w2 = v2f{kc.y, kc.y} * sgn;
                     vdit(a, b, kc, w2, v[q0], v[q1]);
@@ -163,42 +138,22 @@ __device__ __forceinline__ void dit_stages(v2f (&v)[NREG], v2f wfine = v2f{1.0f,
             // twiddles of the first half of the stage (c < half/2); the rest are these times -i
             constexpr int NCMAX = NREG / 4 > 0 ? NREG / 4 : 1;
             const int nc = half > 1 ? half / 2 : 1;
-            v2f tw[NCMAX], tw2[NCMAX], twr[NCMAX];
+            v2f tw[NCMAX];
 #pragma unroll
             for (int c = 0; c < NCMAX; ++c) {
                 if (c >= nc) continue;
                 const int kidx = c * (16 >> rb);
                 const v2f kc = {W32_RE[kidx & 15], W32_IM[kidx & 15]};
                 tw[c] = c == 0 ? base : vcmul(base, kc);
-                if (!RC_ASMNEG) {
-                    tw2[c] = __builtin_shufflevector(tw[c], tw[c], 1, 1) * sgn;
-                    twr[c] = __builtin_shufflevector(tw[c], tw[c], 0, 0) * (-sgn);
-                }
             }
-            if (RC_BF2 && RC_ASMNEG) {
-                // butterfly i of the stage: q0 = the i-th register index with bit rb clear
+            // butterfly i of the stage: q0 = the i-th register index with bit rb clear
 #pragma unroll
-                for (int i = 0; i < NREG / 2; i += 2) {
-                    const int qa = ((i >> rb) << (rb + 1)) | (i & (half - 1)), qb = (((i + 1) >> rb) << (rb + 1)) | ((i + 1) & (half - 1));
-                    const int ca_ = qa & (half - 1), cb_ = qb & (half - 1);
-                    v2f a0 = v[qa], b0 = v[qa | half], a1 = v[qb], b1 = v[qb | half];
-                    vdit2_m<CONJ>(a0, b0, tw[ca_ < nc ? ca_ : ca_ - nc], ca_ >= nc, a1, b1, tw[cb_ < nc ? cb_ : cb_ - nc], cb_ >= nc);
-                    v[qa] = b0, v[qa | half] = a0, v[qb] = b1, v[qb | half] = a1;
-                }
-            } else
-#pragma unroll
-            for (int q0 = 0; q0 < NREG; ++q0) {
-                if (q0 & half) continue;
-                const int q1 = q0 | half;
-                const int c = q0 & (half - 1);
-                const v2f a = v[q0], b = v[q1];
-                if (RC_ASMNEG) {
-                    if (c < nc) vdit_m<CONJ>(a, b, tw[c], v[q0], v[q1]);
-                    else vdit_rot_m<CONJ>(a, b, tw[c - nc], v[q0], v[q1]);
-                } else {
-                    if (c < nc) vdit(a, b, tw[c], tw2[c], v[q0], v[q1]);
-                    else vdit_rot(a, b, tw[c - nc], twr[c - nc], v[q0], v[q1]);
-                }
+            for (int i = 0; i < NREG / 2; i += 2) {
+                const int qa = ((i >> rb) << (rb + 1)) | (i & (half - 1)), qb = (((i + 1) >> rb) << (rb + 1)) | ((i + 1) & (half - 1));
+                const int ca_ = qa & (half - 1), cb_ = qb & (half - 1);
+                v2f a0 = v[qa], b0 = v[qa | half], a1 = v[qb], b1 = v[qb | half];
+                vdit2_m<CONJ>(a0, b0, tw[ca_ < nc ? ca_ : ca_ - nc], ca_ >= nc, a1, b1, tw[cb_ < nc ? cb_ : cb_ - nc], cb_ >= nc);
+                v[qa] = b0, v[qa | half] = a0, v[qb] = b1, v[qb | half] = a1;
             }
         }
     }
@@ -232,12 +187,10 @@ __device__ __forceinline__ void pair_regs(float2 A, float2 Bp, float2 w, uint32_
 // The same pair in packed (re,im) arithmetic: 17 v_pk_* + 10 transcendental + the two hashes instead
 // of ~50 scalar VALU ops. A wave issues one VALU instruction per ~4.75 cycles whatever it is, so the
 // instruction count, not the flop count, sets the middle stage's time (profiles/r01e stamps).
-#ifndef RC_PAIR_PK
-#define RC_PAIR_PK 1
-#endif
+template <bool MAD16 = true>
 __device__ __forceinline__ void phase_cs2_x(uint32_t x, v2f &lo, v2f &up) {
     float a, b, c, d;
-    phase_ncs2_x(x, a, b, c, d);
+    phase_ncs2_x<MAD16>(x, a, b, c, d);
     lo = v2f{a, b};
     up = v2f{c, d};
 }
@@ -296,8 +249,9 @@ __device__ __forceinline__ v2f cmulc_fma(v2f a, v2f w, v2f t) {
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(w), "v"(t));
     return r;
 }
-// BAND: gq = the gains of bins ja and M - ja (the curated band-mask kernel RC_DK_BAND, fused: |g X| = |g| |X|)
-template <int LOG2N, bool DC = false, bool BAND = false>
+// BAND: gq = the gains of bins ja and M - ja (the curated band-mask kernel RC_DK_BAND, fused: |g X| = |g| |X|);
+// MAD16: the form of the upper phase mantissa (phase_rev_upper)
+template <int LOG2N, bool DC = false, bool BAND = false, bool MAD16 = true>
 __device__ __forceinline__ void pair_regs_pk4(v2f A, v2f Bp, v2f w, uint32_t x1, PhaseKey key, v2f &VA,
                                               v2f &VB, bool dc = false, v2f gq = v2f{1.0f, 1.0f}) {
     constexpr uint32_t N = 1u << LOG2N, M = N / 2;
@@ -312,8 +266,8 @@ __device__ __forceinline__ void pair_regs_pk4(v2f A, v2f Bp, v2f w, uint32_t x1,
     v2f mm = v2f{__builtin_amdgcn_sqrtf(q2.x), __builtin_amdgcn_sqrtf(q2.y)};
     if constexpr (BAND) mm = mm * gq;
     v2f cs1, cs2, cs3, cs4;
-    phase_cs2_x(x1, cs1, cs4);       // bins ja and M + ja
-    phase_cs2_x(cM - x1, cs3, cs2);  // bins M - ja and N - ja
+    phase_cs2_x<MAD16>(x1, cs1, cs4);       // bins ja and M + ja
+    phase_cs2_x<MAD16>(cM - x1, cs3, cs2);  // bins M - ja and N - ja
     if (DC) {
         cs2 = vsel(dc, cs1, cs2);
         cs3 = vsel(dc, cs4, cs3);
@@ -422,10 +376,7 @@ __device__ constexpr HannK HANN_E14 = make_hann_k(HANN_ENV_AMP, 8192, 16);
 // synthesis window times -1/(4N) = -2^-16 (hop4: the scale of the magnitudes, src/fft.rs:72's / N and the sign
 // of the negated phasors, moved out of the per-bin stage; a power of two, so nothing rounds differently)
 // (round 6: pair_regs_pk5 returns half of pair_regs_pk4's values, so with it the scale is -1/(2N) = -2^-15)
-#ifndef RC_FOLDPROD
-#define RC_FOLDPROD 1  // the Hermitian fold as a product (pair_regs_pk5); 0: as a sum of two phasors (pair_regs_pk4), for A/B
-#endif
-constexpr double HANN_KAPPA = (RC_FOLDPROD ? -0.5 : -0.25) / 16384.0;
+constexpr double HANN_KAPPA = -0.5 / 16384.0;
 __device__ constexpr HannK HANN_W14K = make_hann_k(0.5 * HANN_KAPPA, 16384, 32);
 
 }  // namespace

@@ -1,10 +1,7 @@
 // N = 16384 (the reference's default window, src/main.rs:31-36): hop4_kernel (default hanning window; the kernel
-// bench.py measures) and hop2_kernel's table variant (caller-supplied window). DESIGN.md 5.1b / 5.1d.
+// bench.py measures) and hop2_kernel (caller-supplied window at pitch != 1). DESIGN.md 5.1b / 5.1d.
 #include "rc_dit.hpp"
 
-#ifndef RC_HOP4_BUFLOAD
-#define RC_HOP4_BUFLOAD 1  // hop4's input rows through buffer loads (0: global loads with 64-bit lane addresses, for A/B)
-#endif
 namespace rc {
 namespace {
 
@@ -41,18 +38,17 @@ constexpr int f3_idx(int n) {
     return r;
 }
 
-template <bool PITCH1, bool HANN>
+// A caller-supplied window at pitch != 1: analysis / synthesis window and envelope come from the engine's tables.
 __global__ __launch_bounds__(256, 2) void hop2_kernel(const HopParams p) {
     constexpr int LOG2N = 14, m = 13, M = 1 << m, H = M, T = 256, P = 32, PH = 16;
     constexpr int RES = 512;                      // residues of the last forward pass
     constexpr int SCR = HOP2_XBUF + 8;            // 32-element scratch for thread 0's pairs
-    // per-workgroup twiddle / window-rotation tables (filled once per run): the hop loop itself has
-    // no table loads from global memory
+    // per-workgroup twiddle tables (filled once per run): the hop loop itself has no table loads from global memory
     constexpr int T_A = SCR + 32;                 // [256] W_8192^t
     constexpr int T_R = T_A + 256;                // [256] W_16384^t
     constexpr int T_B = T_R + 256;                // [16]  W_512^l
     constexpr int T_C = T_B + 16;                 // [24]  W_64^k, k <= 16
-    constexpr int T_H = T_C + 24;                 // [1024] HANN: hann_rot as float2 pairs
+    constexpr int T_H = T_C + 24;                 // [1024] unused; kept so the launch's LDS size (and occupancy) stays
     static_assert(T_H + 1024 == HOP2_LDS_FLOAT2, "LDS layout");
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
     const int tid = threadIdx.x;
@@ -67,7 +63,7 @@ __global__ __launch_bounds__(256, 2) void hop2_kernel(const HopParams p) {
     GFW outc = (GFW)p.out + (size_t)ch * p.out_stride;
     const unsigned lane2 = 2u * (unsigned)tid;
     GV2 wtab = (GV2)p.wtab;
-    const uint32_t pitch = PITCH1 ? 1u : p.pitch;
+    const uint32_t pitch = p.pitch;
 
     // residues of this thread and per-thread LDS bases (thread part of every access pattern)
     const int r = tid, rb = tid ? RES - tid : RES / 2;
@@ -91,23 +87,8 @@ __global__ __launch_bounds__(256, 2) void hop2_kernel(const HopParams p) {
         lds[T_R + tid] = ldg2((GV2)p.rtab + tid);
         if (tid < 16) lds[T_B + tid] = ldg2(wtab + 16 * tid);
         if (tid <= 16) lds[T_C + tid] = ldg2(wtab + 128 * tid);
-        if constexpr (HANN) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {  // (cos, sin) of e = 0, 1 -> (cos e0, cos e1), (sin e0, sin e1)
-                const float2 a = ldg2((GV2)p.hann_rot + 512 * i + 2 * tid);
-                const float2 b = ldg2((GV2)p.hann_rot + 512 * i + 2 * tid + 1);
-                lds[T_H + 512 * i + 2 * tid] = make_float2(a.x, b.x);
-                lds[T_H + 512 * i + 2 * tid + 1] = make_float2(a.y, b.y);
-            }
-        }
         __syncthreads();
     }
-    // The hop loop is software-pipelined (RC_SWP): the LDS stores of an exchange drain for ~800
-    // cycles during which the wave would only wait at the barrier, so the next hop's window multiply
-    // and first pass F1 (registers only) run between the E3 store and its barrier; the next hop's
-    // samples are requested before I1. vn carries F1's output into the next iteration.
-    //   RC_SWP = 0: plain order
-    constexpr bool SWP = RC_SWP != 0 && HANN;  // (the table-window variant has no registers to spare)
     float xr0[P], xr1[P];
     auto issue_x = [&](int64_t kk) {
         GF src = hop_src(p, xc, xt, kk);
@@ -119,109 +100,53 @@ __global__ __launch_bounds__(256, 2) void hop2_kernel(const HopParams p) {
     };
     // register q of vn := z[brev5(q) * T + t] * window, then F1 (bits 0..4, constants only)
     auto win_f1 = [&](v2f (&vn)[P]) {
-        if constexpr (HANN) {
-            const v2f cb = to_v(lds[T_H + 2 * tid]), sb = to_v(lds[T_H + 2 * tid + 1]);
-            const v2f half = {0.5f, 0.5f};
+        GF win = per_hop(p.window);
+        float wr0[P], wr1[P];
 #pragma unroll
-            for (int q = 0; q < P; ++q) {  // packed: 3 instructions per sample pair
-                const v2f wq = __builtin_elementwise_fma(v2f{HANN_W14.s[q], HANN_W14.s[q]}, sb,
-                               __builtin_elementwise_fma(v2f{HANN_W14.c[q], HANN_W14.c[q]}, cb, half));
-                vn[brev_c(q, 5)] = v2f{xr0[q], xr1[q]} * wq;
-            }
-        } else {
-            GF win = per_hop(p.window);
-            float wr0[P], wr1[P];
-#pragma unroll
-            for (int q = 0; q < P; ++q) {
-                wr0[q] = (win + 2 * T * q)[lane2];
-                wr1[q] = (win + 2 * T * q)[lane2 + 1];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < P; ++q) vn[brev_c(q, 5)] = v2f{xr0[q], xr1[q]} * v2f{wr0[q], wr1[q]};
+        for (int q = 0; q < P; ++q) {
+            wr0[q] = (win + 2 * T * q)[lane2];
+            wr1[q] = (win + 2 * T * q)[lane2 + 1];
         }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < P; ++q) vn[brev_c(q, 5)] = v2f{xr0[q], xr1[q]} * v2f{wr0[q], wr1[q]};
         __builtin_amdgcn_sched_barrier(0);
         st.mark(0);
         dit_stages<32, m, 0, 4, 0, false, false>(vn);
         st.mark(1);
     };
-    // epilogue of hop kk (ve = its I3 output): synthesis window, overlap-add with the carried tail,
-    // store. With RC_SWP >= 2 it runs one iteration late, under the next hop's E1 store drain.
+    // epilogue of hop kk (ve = its I3 output): synthesis window, overlap-add with the carried tail, store
     auto epilogue = [&](int64_t kk, v2f (&ve)[P]) {
-        // ---- epilogue: synthesis window, overlap-add with the carried tail, store
-        // HANN: (cos, cos) / (sin, sin) of this thread's beta for samples e = 0, 1 (window, envelope)
-        v2f cbW = {0.f, 0.f}, sbW = cbW, cbE = cbW, sbE = cbW;
-        const v2f half2 = {0.5f, 0.5f};
-        if constexpr (HANN) {
-            cbW = to_v(lds[T_H + 2 * tid]), sbW = to_v(lds[T_H + 2 * tid + 1]);
-            cbE = to_v(lds[T_H + 2 * T + 2 * tid]), sbE = to_v(lds[T_H + 2 * T + 2 * tid + 1]);
+        GF wsrc = per_hop(p.window);
+        float wr0[P], wr1[P];
 #pragma unroll
-            for (int q = 0; q < P; ++q)
-                ve[q] *= __builtin_elementwise_fma(v2f{HANN_W14.s[q], HANN_W14.s[q]}, sbW,
-                        __builtin_elementwise_fma(v2f{HANN_W14.c[q], HANN_W14.c[q]}, cbW, half2));
-            __builtin_amdgcn_sched_barrier(0);
-        } else {
-            GF wsrc = per_hop(p.window);
-            float wr0[P], wr1[P];
-#pragma unroll
-            for (int q = 0; q < P; ++q) {
-                wr0[q] = (wsrc + 2 * T * q)[lane2];
-                wr1[q] = (wsrc + 2 * T * q)[lane2 + 1];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < P; ++q) ve[q] *= v2f{wr0[q], wr1[q]};
-            __builtin_amdgcn_sched_barrier(0);
+        for (int q = 0; q < P; ++q) {
+            wr0[q] = (wsrc + 2 * T * q)[lane2];
+            wr1[q] = (wsrc + 2 * T * q)[lane2 + 1];
         }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < P; ++q) ve[q] *= v2f{wr0[q], wr1[q]};
+        __builtin_amdgcn_sched_barrier(0);
         if (kk >= k_begin) {
             const int64_t g0 = kk * (int64_t)H;
             GF esrc = per_hop(p.env);
-            if constexpr (PITCH1) {
-                GFW dst = outc + (g0 - p.out_origin);
-                float er0[PH], er1[PH];
-                if constexpr (!HANN) {
+            const int64_t kq = g0 / pitch;
+            const uint32_t kr = (uint32_t)(g0 % pitch);
+            GFW dst = outc + (kq - p.out_origin);
+            int t2 = tid;
+            opaque(t2);
 #pragma unroll
-                    for (int q = 0; q < PH; ++q) {
-                        er0[q] = (esrc + 2 * T * q)[lane2];
-                        er1[q] = (esrc + 2 * T * q)[lane2 + 1];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                const v2f amp2 = {p.amp, p.amp};
-#pragma unroll
-                for (int q = 0; q < PH; ++q) {
-                    v2f er;
-                    if constexpr (HANN)
-                        er = __builtin_elementwise_fma(v2f{HANN_E14.s[q], HANN_E14.s[q]}, sbE,
-                             __builtin_elementwise_fma(v2f{HANN_E14.c[q], HANN_E14.c[q]}, cbE, half2));
-                    else
-                        er = v2f{er0[q], er1[q]};
-                    // stretcher.rs:97-100 operation order, both samples of the pair per instruction
-                    const v2f o = (ve[q] + tail[q]) * er * amp2;
-                    *(GV2W)(dst + 2 * T * q + lane2) = o;
-                }
-            } else {
-                const int64_t kq = g0 / pitch;
-                const uint32_t kr = (uint32_t)(g0 % pitch);
-                GFW dst = outc + (kq - p.out_origin);
-                int t2 = tid;
-                opaque(t2);
-#pragma unroll
-                for (int q = 0; q < PH; ++q) {
-                    const uint32_t i0 = 2u * (uint32_t)(t2 + T * q);
-                    v2f er;
-                    if constexpr (HANN)
-                        er = __builtin_elementwise_fma(v2f{HANN_E14.s[q], HANN_E14.s[q]}, sbE,
-                             __builtin_elementwise_fma(v2f{HANN_E14.c[q], HANN_E14.c[q]}, cbE, half2));
-                    else
-                        er = v2f{(esrc + 2 * T * q)[lane2], (esrc + 2 * T * q)[lane2 + 1]};
-                    const v2f o = (ve[q] + tail[q]) * er * v2f{p.amp, p.amp};
-                    const float o0 = o.x, o1 = o.y;
-                    const uint32_t a0 = kr + i0, a1 = a0 + 1;
-                    const uint32_t d0 = a0 / pitch, d1 = a1 / pitch;
-                    if (d0 * pitch == a0) dst[d0] = o0;
-                    if (d1 * pitch == a1) dst[d1] = o1;
-                }
+            for (int q = 0; q < PH; ++q) {
+                const uint32_t i0 = 2u * (uint32_t)(t2 + T * q);
+                const v2f er = v2f{(esrc + 2 * T * q)[lane2], (esrc + 2 * T * q)[lane2 + 1]};
+                // stretcher.rs:97-100 operation order, both samples of the pair per instruction
+                const v2f o = (ve[q] + tail[q]) * er * v2f{p.amp, p.amp};
+                const float o0 = o.x, o1 = o.y;
+                const uint32_t a0 = kr + i0, a1 = a0 + 1;
+                const uint32_t d0 = a0 / pitch, d1 = a1 / pitch;
+                if (d0 * pitch == a0) dst[d0] = o0;
+                if (d1 * pitch == a1) dst[d1] = o1;
             }
         }
 #pragma unroll
@@ -229,24 +154,15 @@ __global__ __launch_bounds__(256, 2) void hop2_kernel(const HopParams p) {
         st.mark(21);
     };
     const int64_t k_first = k_begin > 0 ? k_begin - 1 : k_begin;
-    constexpr bool SWP2 = SWP && RC_SWP >= 2;
-    v2f vo[P];  // SWP2: I3 output of the previous hop, its epilogue still to run
     v2f vn[P];
-    if constexpr (SWP) issue_x(k_first);
-    if constexpr (SWP) win_f1(vn);
     for (int64_t k = k_first; k < k_end; ++k) {
         const PhaseKey key = make_phase_key(p.seed_mixed, p.ch_first + ch, k);
         v2f v[P];
-        if constexpr (!SWP) {
-            issue_x(k);
-            win_f1(vn);
-        }
+        issue_x(k);
+        win_f1(vn);
         // ---- forward: F1 (done), E1, F2 (bits 5..8), E2, F3 (bits 9..12)
 #pragma unroll
         for (int q = 0; q < P; ++q) lds[bE1s + f3_idx(q)] = to_f2(vn[q]);
-        if constexpr (SWP2) {
-            if (k > k_first) epilogue(k - 1, vo);
-        }
         st.mark(2);
         __syncthreads();
         st.mark(3);
@@ -297,7 +213,6 @@ __global__ __launch_bounds__(256, 2) void hop2_kernel(const HopParams p) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 // exp(-2 pi i (r + 512 q) / N) = wr * W32^q
-#if RC_PAIR_PK
                 const v2f wrv = to_v(wr);
                 const v2f wq = q == 0 ? wrv : (q == 8 ? v2f{wr.y, -wr.x}
                                : vcmul(wrv, v2f{W32_RE[q & 15], W32_IM[q & 15]}));
@@ -305,14 +220,6 @@ __global__ __launch_bounds__(256, 2) void hop2_kernel(const HopParams p) {
                 pair_regs_pk<LOG2N>(va[q], vb[15 - q], wq, x0 + (uint32_t)q * dx, key, VA, VB);
                 va[q] = VA;
                 vb[15 - q] = VB;
-#else
-                const float2 wq = q == 0 ? wr : (q == 8 ? make_float2(wr.y, -wr.x)
-                                  : cmul(wr, make_float2(W32_RE[q & 15], W32_IM[q & 15])));
-                float2 VA, VB;
-                pair_regs<LOG2N>(to_f2(va[q]), to_f2(vb[15 - q]), wq, x0 + (uint32_t)q * dx, key, VA, VB);
-                va[q] = to_v(VA);
-                vb[15 - q] = to_v(VB);
-#endif
             }
         }
         st.mark(10);
@@ -340,7 +247,6 @@ __global__ __launch_bounds__(256, 2) void hop2_kernel(const HopParams p) {
             }
         }
         st.mark(11);
-        if constexpr (SWP) issue_x(k + 1 < k_end ? k + 1 : k);  // (the last hop re-reads itself)
         // ---- inverse: I1 in registers (position bits 0..3 = brev4 of the register index)
         v2f pa[16], pb[16];
 #pragma unroll
@@ -357,7 +263,6 @@ __global__ __launch_bounds__(256, 2) void hop2_kernel(const HopParams p) {
             lds[bE3b + f3_idx(q)] = to_f2(pb[q]);
         }
         st.mark(13);
-        if constexpr (SWP) win_f1(vn);  // next hop's window + F1 while the E3 stores drain
         __syncthreads();
         st.mark(14);
 #pragma unroll
@@ -377,14 +282,8 @@ __global__ __launch_bounds__(256, 2) void hop2_kernel(const HopParams p) {
         dit_stages<32, m, 9, 12, 8, true, true>(v, to_v(lds[T_A + tid]));
         st.mark(20);
 
-        if constexpr (SWP2) {
-#pragma unroll
-            for (int q = 0; q < P; ++q) vo[q] = v[q];
-        } else {
-            epilogue(k, v);
-        }
+        epilogue(k, v);
     }
-    if constexpr (SWP2) epilogue(k_end - 1, vo);
 #if RC_STAMP
     if ((tid & 63) == 0 && p.spec) {
         unsigned *dbg = (unsigned *)p.spec + ((size_t)blockIdx.x * (T / 64) + (tid >> 6)) * 32;
@@ -426,11 +325,6 @@ __device__ __forceinline__ void wave_fence() {
 
 // Workgroup barrier of the hop loop. __syncthreads() also waits for vmcnt(0), i.e. for the previous hop's
 // output stores to be acknowledged; the exchanges only need this wave's LDS operations to have completed.
-#if RC_FOLDPROD
-#define HOP4_PAIR pair_regs_pk5
-#else
-#define HOP4_PAIR pair_regs_pk4
-#endif
 #define HOP4_BAR()                                                                    \
     do {                                                                              \
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                \
@@ -583,7 +477,7 @@ __global__ __launch_bounds__(256, 3) void hop4_kernel(const HopParams p) {
             typedef unsigned v2u __attribute__((ext_vector_type(2)));
 #define HOP4_STORE(o, row)                                                                                                  \
     do {                                                                                                                    \
-        if constexpr (RC_HOP4_BUFLOAD && !TABW)                                                                             \
+        if constexpr (!TABW)                                                                             \
             __builtin_amdgcn_raw_buffer_store_b64(v2u{__float_as_uint((o).x), __float_as_uint((o).y)}, rd,                 \
                                                   (int)(4u * lane2), 4 * 2 * T * (row), 2);                                 \
         else __builtin_nontemporal_store(o, (GV2W)(dst + 2 * T * (row) + lane2));                                           \
@@ -682,7 +576,7 @@ __global__ __launch_bounds__(256, 3) void hop4_kernel(const HopParams p) {
         {   // register brev5(q) := z[q * T + t] * window ; F1 = stages 0..4
             GF src = hop_src(p, xc, xt, k);
             float xr0[P], xr1[P];
-            if constexpr (RC_HOP4_BUFLOAD && !TABW) {
+            if constexpr (!TABW) {
                 // buffer loads: the hop's base in a resource descriptor (SGPRs), ONE 32-bit lane offset for all rows, the row
                 // in the scalar offset - no 64-bit VALU address arithmetic (the global_load form spent 2 x 16 v_add_co /
                 // v_addc per hop and wave on it, with an address pair live per two rows). Not in the table-window
@@ -862,9 +756,9 @@ __global__ __launch_bounds__(256, 3) void hop4_kernel(const HopParams p) {
                     gq = v2f{band_gain(p, ja), band_gain(p, (uint32_t)M - ja)};
                 }
                 if (q == 0)
-                    HOP4_PAIR<LOG2N, true, BAND>(va[q], vb[15 - q], wq, x0, key, VA, VB, is0, gq);
+                    pair_regs_pk5<LOG2N, true, BAND>(va[q], vb[15 - q], wq, x0, key, VA, VB, is0, gq);
                 else
-                    HOP4_PAIR<LOG2N, false, BAND>(va[q], vb[15 - q], wq, (q < 8 ? x0 : x0h) + (uint32_t)q * dx, key, VA, VB,
+                    pair_regs_pk5<LOG2N, false, BAND>(va[q], vb[15 - q], wq, (q < 8 ? x0 : x0h) + (uint32_t)q * dx, key, VA, VB,
                                                   false, gq);
                 va[q] = VA;
                 vb[15 - q] = VB;
@@ -875,7 +769,7 @@ __global__ __launch_bounds__(256, 3) void hop4_kernel(const HopParams p) {
             // bin 4096 = M / 2 pairs with itself: exp(-2 pi i 4096 / N) = -i, counter of bin 4096
             v2f V8, V8b;
             const float g8 = BAND ? band_gain(p, 8u * (uint32_t)RES) : 1.0f;
-            HOP4_PAIR<LOG2N, false, BAND>(s8, s8, v2f{0.0f, -1.0f}, 8u * (uint32_t)RES * key.mul + key.k0, key, V8, V8b,
+            pair_regs_pk5<LOG2N, false, BAND>(s8, s8, v2f{0.0f, -1.0f}, 8u * (uint32_t)RES * key.mul + key.k0, key, V8, V8b,
                                           false, v2f{g8, g8});
             v2f na[8], nb0[8], nb1[8];
 #pragma unroll
@@ -1055,26 +949,15 @@ __global__ __launch_bounds__(256, 3) void hop4_kernel(const HopParams p) {
 
 }  // namespace
 
-#ifndef RC_HOP4_TABW
-#define RC_HOP4_TABW 1  // a caller's window at pitch 1 through hop4_kernel<1, false, true> (0: hop2_kernel, for A/B)
-#endif
-#ifndef RC_PITCHC
-#define RC_PITCHC 1  // pitch 2 and 3 run instantiations with the pitch at compile time (0: the runtime-pitch kernel, for A/B)
-#endif
-// N = 16384, fused path: default hanning window -> hop4_kernel (optionally with the band mask in its pair stage),
-// caller-supplied window -> hop2_kernel's table variant. The test-hook library (RC_TEST_HOOKS) can also run the
-// previous generation (hop3_kernel, rc_hop16k_prev.hip) and hop2_kernel's computed-window variant for A/B runs.
+// N = 16384, fused path: default hanning window -> hop4_kernel (optionally with the band mask in its pair stage; pitch 2
+// and 3 run instantiations with the pitch at compile time), caller-supplied window -> hop4_kernel's table variant at
+// pitch 1, hop2_kernel at other pitches. The test-hook library (RC_TEST_HOOKS) can also run the previous generation
+// (hop3_kernel, rc_hop16k_prev.hip) for A/B runs.
 hipError_t launch_hop16k(const HopParams &p, hipStream_t s) {
     const dim3 grid(p.runs_per_channel * p.n_channels), block(256);
     const bool hann = p.hann_rot != nullptr;
 #if RC_TEST_HOOKS
     if (hann && (p.diag_flags & RC_DIAG_PREV_KERNEL)) return launch_hop16k_prev(p, s);
-    if (hann && (p.diag_flags & RC_DIAG_HOP2_HANN)) {
-        const size_t lds2 = sizeof(float2) * (size_t)HOP2_LDS_FLOAT2;
-        if (p.pitch == 1) hipLaunchKernelGGL((hop2_kernel<true, true>), grid, block, lds2, s, p);
-        else hipLaunchKernelGGL((hop2_kernel<false, true>), grid, block, lds2, s, p);
-        return hipGetLastError();
-    }
 #endif
     if (hann) {
         const size_t lds4 = sizeof(float2) * (size_t)HOP4_LDS_FLOAT2;
@@ -1082,18 +965,16 @@ hipError_t launch_hop16k(const HopParams &p, hipStream_t s) {
             if (p.pitch == 1) hipLaunchKernelGGL((hop4_kernel<1, true>), grid, block, lds4, s, p);
             else hipLaunchKernelGGL((hop4_kernel<0, true>), grid, block, lds4, s, p);
         } else if (p.pitch == 1) hipLaunchKernelGGL((hop4_kernel<1>), grid, block, lds4, s, p);
-        else if (p.pitch == 2 && RC_PITCHC) hipLaunchKernelGGL((hop4_kernel<2>), grid, block, lds4, s, p);
-        else if (p.pitch == 3 && RC_PITCHC) hipLaunchKernelGGL((hop4_kernel<3>), grid, block, lds4, s, p);
+        else if (p.pitch == 2) hipLaunchKernelGGL((hop4_kernel<2>), grid, block, lds4, s, p);
+        else if (p.pitch == 3) hipLaunchKernelGGL((hop4_kernel<3>), grid, block, lds4, s, p);
         else hipLaunchKernelGGL((hop4_kernel<0>), grid, block, lds4, s, p);
     } else {
         if (!p.window || !p.env) return hipErrorInvalidValue;  // (the table-window kernels dereference both)
-        const size_t lds2 = sizeof(float2) * (size_t)HOP2_LDS_FLOAT2;
         // pitch 1: hop4 with table windows (three workgroups per CU, run tickets, seams: hop_workgroups_per_cu says so
         // to the planner); other pitches: hop2_kernel
-        if (p.pitch == 1 && RC_HOP4_TABW)
+        if (p.pitch == 1)
             hipLaunchKernelGGL((hop4_kernel<1, false, true>), grid, block, sizeof(float2) * (size_t)HOP4_LDS_FLOAT2, s, p);
-        else if (p.pitch == 1) hipLaunchKernelGGL((hop2_kernel<true, false>), grid, block, lds2, s, p);
-        else hipLaunchKernelGGL((hop2_kernel<false, false>), grid, block, lds2, s, p);
+        else hipLaunchKernelGGL(hop2_kernel, grid, block, sizeof(float2) * (size_t)HOP2_LDS_FLOAT2, s, p);
     }
     return hipGetLastError();
 }

@@ -22,13 +22,12 @@
 //     and the first hop of a run is recomputed (phases are a pure function of (seed,c,k,j)).
 // No MFMA: this is an FFT/SFU/LDS-bound path, not a contraction.
 #include "rc_passes.hpp"
-#ifndef RC_HOPW
-#define RC_HOPW 31  // default window: bit 0 N = 4096 runs hopw_kernel, bit 1 N = 8192 hopw2_kernel, bit 2 N = 2048 hopw11_kernel, bit 3 N = 1024 hopw10_kernel, bit 4 N = 512 hopw9_kernel (0: generic, for A/B)
-#endif
 #include "rc_dit.hpp"  // (the constexpr sine / cosine of the computed-window constants)
 
 namespace rc {
 namespace {
+
+constexpr int LOADCH = 32;  // window rows the resynthesis epilogue loads per batch
 
 // pA / pB: padded LDS indices of bins ja and M - ja
 template <int LOG2N, int MODE>
@@ -265,7 +264,7 @@ __global__ __launch_bounds__((Geo<LOG2N>::T * hop_slots_of<LOG2N, MODE>()), Geo<
             inverse_passes<G, G::m>(v, lds, ctx, wtab, st);
             GFW y = (GFW)p.ybuf + hop_idx * N;
             GF wsrc = per_hop(p.window);
-            constexpr int CH = P < RC_LOADCH ? P : RC_LOADCH;
+            constexpr int CH = P < LOADCH ? P : LOADCH;
 #pragma unroll
             for (int q0 = 0; q0 < P; q0 += CH) {
 #pragma unroll
@@ -437,9 +436,7 @@ hipError_t launch_hop_n(HopMode mode, const HopParams &p, hipStream_t s) {
             else {
                 // 512 ... 8192: the wave-local kernels (rc_hopw.hip), default window or a caller's; the generic kernel's
                 // fused instantiations then serve the shorter lengths only
-                constexpr bool WL = (LOG2N == 12 && (RC_HOPW & 1)) || (LOG2N == 13 && (RC_HOPW & 2)) || (LOG2N == 11 && (RC_HOPW & 4)) ||
-                                    (LOG2N == 10 && (RC_HOPW & 8)) || (LOG2N == 9 && (RC_HOPW & 16));
-                if constexpr (WL) {
+                if constexpr (LOG2N >= 9) {
                     // (round 5: a caller's window too - the kernels' TABW instantiations read its tables)
                     if constexpr (LOG2N == 12) return launch_hopw(p, s);     // one wave per hop
                     if constexpr (LOG2N == 13) return launch_hopw2(p, s);    // two waves per hop
@@ -471,12 +468,9 @@ hipError_t launch_hop_n(HopMode mode, const HopParams &p, hipStream_t s) {
 }
 }  // namespace
 
-#ifndef RC_HOP4_TABW
-#define RC_HOP4_TABW 1
-#endif
 int hop_workgroups_per_cu(int log2n, bool default_window, bool pitch1) {
     // hop4_kernel: three workgroups per CU - the default window at any pitch, a caller's window at pitch 1 (round 5)
-    return (log2n == 14 && (default_window || (pitch1 && RC_HOP4_TABW))) ? 3 : 0;
+    return (log2n == 14 && (default_window || pitch1)) ? 3 : 0;
 }
 
 int hop_slots(int log2n) {  // runs per workgroup of the fused generic kernel (hop_kernel: one wave holds 64 / T runs below N = 512)
@@ -487,14 +481,12 @@ int hop_slots(int log2n) {  // runs per workgroup of the fused generic kernel (h
 
 int hop_resident_workgroups(int log2n, bool default_window) {
     (void)default_window;  // (round 5: the wave-local kernels serve a caller's window as well)
-    if (log2n == 12 && (RC_HOPW & 1)) return 12;  // hopw_kernel: one wave each, three per SIMD
-    if (log2n == 13 && (RC_HOPW & 2)) return 6;   // hopw2_kernel: two waves each
-#ifndef RC_HOPW11_RES
-#define RC_HOPW11_RES 12  // (16 are resident at 112 VGPRs; 24 runs per CU measured best: 0.635 against 0.65 ms with 16 / 32 / 48)
-#endif
-    if (log2n == 11 && (RC_HOPW & 4)) return RC_HOPW11_RES;  // hopw11_kernel: one wave each
-    if (log2n == 10 && (RC_HOPW & 8)) return 16;  // hopw10_kernel: one wave (two hops at a time) each, four per SIMD
-    if (log2n == 9 && (RC_HOPW & 16)) return 16;  // hopw9_kernel
+    constexpr int HOPW11_RES = 12;  // (16 are resident at 112 VGPRs; 24 runs per CU measured best: 0.635 against 0.65 ms with 16 / 32 / 48)
+    if (log2n == 12) return 12;  // hopw_kernel: one wave each, three per SIMD
+    if (log2n == 13) return 6;   // hopw2_kernel: two waves each
+    if (log2n == 11) return HOPW11_RES;  // hopw11_kernel: one wave each
+    if (log2n == 10) return 16;  // hopw10_kernel: one wave (two hops at a time) each, four per SIMD
+    if (log2n == 9) return 16;   // hopw9_kernel
     return 0;
 }
 

@@ -19,8 +19,7 @@
 // 168 VGPRs and 12 KB of LDS per wave: three waves per SIMD. The first hop of a run is recomputed for its tail (no
 // seam hand-over); a caller-supplied window, pitch != 1 ... all take this kernel except a non-default window (generic).
 // (v_mad_u32_u16 for the upper phase mantissa, rc_dev.hpp: -1.2 % on hop4_kernel, but +1..3 % on the 512 / 1024 / 2048
-// kernels of this file and flat at 4096 / 8192 - same-box A/B, profiles/README.md round 4: not used here)
-#define RC_MAD16 0
+// kernels of this file and flat at 4096 / 8192 - same-box A/B, profiles/README.md round 4: not used here, MAD16 = false)
 #include "rc_dit.hpp"
 
 namespace rc {
@@ -109,9 +108,6 @@ constexpr int H2_TC = H2_TB + 16;                 // [16] W_128^l
 constexpr int H2_TH = H2_TC + 16;                 // [512] window / envelope rotations: thread t at 2 t (+ 256: envelope)
 constexpr int HOPW2_LDS_FLOAT2 = H2_TH + 512;     // 24 896 B
 
-#ifndef RC_HOPW_PREFETCH
-#define RC_HOPW_PREFETCH 1  // hopw11_kernel: next hop's loads before the last inverse pass (0: after the stores, for A/B)
-#endif
 // compiler-only ordering of one wave's LDS accesses (no instruction is emitted)
 __device__ __forceinline__ void wfence() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -235,16 +231,16 @@ __device__ __forceinline__ void hopw_middle(v2f (&va)[NS], v2f (&vb)[NS], const 
                            : vcmul(wrv, v2f{W32_RE[(q * WS) & 15], W32_IM[(q * WS) & 15]}));
             v2f VA, VB;
             if (q == 0)
-                pair_regs_pk4<LOG2N, true>(va[q], vb[NS - 1 - q], wq, x0, key, VA, VB, is0);
+                pair_regs_pk4<LOG2N, true, false, false>(va[q], vb[NS - 1 - q], wq, x0, key, VA, VB, is0);
             else
-                pair_regs_pk4<LOG2N>(va[q], vb[NS - 1 - q], wq, (q < h ? x0 : x0h) + (uint32_t)q * dx, key, VA, VB);
+                pair_regs_pk4<LOG2N, false, false, false>(va[q], vb[NS - 1 - q], wq, (q < h ? x0 : x0h) + (uint32_t)q * dx, key, VA, VB);
             va[q] = VA;
             vb[NS - 1 - q] = VB;
         }
     }
     if (has0) {  // bin M / 2 pairs with itself: exp(-2 pi i (M/2) / N) = -i; then un-deal thread 0's registers
         v2f V8, V8b;
-        pair_regs_pk4<LOG2N>(s8, s8, v2f{0.0f, -1.0f}, (uint32_t)(h * RES) * key.mul + key.k0, key, V8, V8b);
+        pair_regs_pk4<LOG2N, false, false, false>(s8, s8, v2f{0.0f, -1.0f}, (uint32_t)(h * RES) * key.mul + key.k0, key, V8, V8b);
         v2f na[h], nb0[h], nb1[h];
 #pragma unroll
         for (int i = 0; i < h; ++i) {
@@ -576,11 +572,9 @@ __global__ __launch_bounds__(64, 3) void hopw_kernel(const HopParams p) {
 // registers Q6..Q9 (lane = Q0..Q5). Exchange rounds: P3, P6 = the set, Q3 = the set, Q6; 8 stores + 8 loads per round
 // through a buffer of 548 float2. tests/dev/proto_w11.py found and checks the weights. ~100 VGPRs and 7.6 KB of LDS per
 // wave: four waves per SIMD.
-#ifndef RC_HOPW11_WPS
-#define RC_HOPW11_WPS 3  // register budget of three waves per SIMD: the allocator takes 112 VGPRs (four still fit; with the budget of four it takes 94 and the kernel is 6 % slower)
-#endif
+constexpr int HOPW11_WPS = 3;  // register budget of three waves per SIMD: the allocator takes 112 VGPRs (four still fit; with the budget of four it takes 94 and the kernel is 6 % slower)
 template <int PITCHC, bool TABW = false>
-__global__ __launch_bounds__(64, RC_HOPW11_WPS) void hopw11_kernel(const HopParams p) {
+__global__ __launch_bounds__(64, HOPW11_WPS) void hopw11_kernel(const HopParams p) {
     constexpr int LOG2N = 11, m = 10, T = 64, P = 16, PH = 8, RES = 128, NS = 8;
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
     const int tid = threadIdx.x;
@@ -748,7 +742,8 @@ __global__ __launch_bounds__(64, RC_HOPW11_WPS) void hopw11_kernel(const HopPara
                 wfence();
             }
         }
-        if (RC_HOPW_PREFETCH) hopw_load<T, P, true>(hop_src(p, xc, xt, k + 1 < k_end ? k + 1 : k), lane2, xr0, xr1);
+        // next hop's loads before the last inverse pass
+        hopw_load<T, P, true>(hop_src(p, xc, xt, k + 1 < k_end ? k + 1 : k), lane2, xr0, xr1);
         dit_stages<16, m, 6, 9, 6, true, true>(y, to_v(lds[H1_TA + lane()]));
         {
             const int t = lane();
@@ -757,7 +752,6 @@ __global__ __launch_bounds__(64, RC_HOPW11_WPS) void hopw11_kernel(const HopPara
                                         (float)(0.5 * HANN_KAPPA11), pitch, TABW ? per_hop(p.window) + 2 * t : nullptr,
                                         TABW ? per_hop(p.env) + 2 * t : nullptr);
         }
-        if (!RC_HOPW_PREFETCH) hopw_load<T, P, true>(hop_src(p, xc, xt, k + 1 < k_end ? k + 1 : k), lane2, xr0, xr1);
     }
 }
 

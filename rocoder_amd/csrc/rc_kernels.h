@@ -8,11 +8,6 @@ namespace rc {
 
 // One launch = channels [0, n_channels) x hops [hop_first, hop_first + hop_count), cut into
 // `runs_per_channel` contiguous runs of `run_len` hops; one workgroup walks one run.
-// 0: variant builds only (tools/build_variant.sh x -DRC_BLUESTEIN=0) - window lengths that are not a power of two run
-// the first implementation's O(N^2) DFT kernels instead of the chirp-z transforms, as an independent A/B partner
-#ifndef RC_BLUESTEIN
-#define RC_BLUESTEIN 1
-#endif
 
 struct HopParams {
     const float *x;        // channel c at x + c * in_stride; x[0] is absolute sample `in_origin`
@@ -71,7 +66,7 @@ struct HopParams {
     uint32_t n_generic;
     const float2 *tw_generic;
     // ... of them, the lengths N <= 16384 run chirp-z (Bluestein) transforms of the packed N/2-point sequence in LDS:
-    // bl_log2l = log2 of the convolution length L >= N - 1 (0: the O(N^2) DFT kernels), bl_tab = [N/2] chirp
+    // bl_log2l = log2 of the convolution length L >= N - 1, bl_tab = [N/2] chirp
     // exp(-i pi n^2 / (N/2)) | [L/2] exp(-2 pi i k / L) | [L] FFT_L of the conjugate chirp / L in bit-reversed order
     uint32_t bl_log2l;
     const float2 *bl_tab;
@@ -152,8 +147,6 @@ constexpr uint32_t RC_DIAG_SKIP_SEAM_PUBLISH = 1;
 // run the previous kernel generation of the N = 16384 path (hop3) instead of hop4: A/B timing and the
 // bit-exactness test between the two. Only the test-hook library (-DRC_TEST_HOOKS=1, `make hooks`) contains it.
 constexpr uint32_t RC_DIAG_PREV_KERNEL = 2;
-// test-hook library only: hop2_kernel's computed-window variant (two workgroups per CU) instead of hop4
-constexpr uint32_t RC_DIAG_HOP2_HANN = 4;
 // test-hook library only: N = 65536 through big4_kernel<64> (round 4's kernel) instead of big5_kernel: A/B partner
 constexpr uint32_t RC_DIAG_BIG4_64 = 8;
 #ifndef RC_TEST_HOOKS
@@ -239,7 +232,7 @@ struct DevKernelParams {
 hipError_t launch_dev_kernel(const DevKernelParams &p, hipStream_t s);
 
 // Window lengths that are not a power of two (any even N): the reference accepts them through rustfft
-// (src/main.rs:34, src/fft.rs:27-29). They run as plain O(N^2) DFTs on the device - correct, not fast:
+// (src/main.rs:34, src/fft.rs:27-29). They run as chirp-z transforms on the device (rc_misc.hip):
 //   stage 0: X[k] = sum_n x[k_hop step + n] w[n] e^{-2 pi i n k / N}   -> p.spec (natural order, all N bins)
 //   stage 1: Z[k] = |X[k]| e^{i theta(seed, c, hop, k)}                 (in place)
 //   stage 2: y[n] = Re(sum_k Z[k] e^{+2 pi i n k / N}) / N * w[n]       -> p.ybuf

@@ -1,5 +1,5 @@
 // Small kernels around the hop kernels: gather-form overlap-add (user-kernel path, negative pitch), curated
-// device frequency kernels, O(N^2) DFTs for window lengths that are not a power of two, the per-job prep launch.
+// device frequency kernels, chirp-z transforms for window lengths that are not a power of two, the per-job prep launch.
 #include "rc_dev.hpp"
 
 namespace rc {
@@ -84,34 +84,6 @@ hipError_t launch_dev_kernel(const DevKernelParams &p, hipStream_t s) {
 }
 
 // ---- window lengths that are not a power of two (rc_kernels.h, launch_gen) -----------
-#if !RC_BLUESTEIN
-// O(N^2) DFTs: the first implementation, kept for A/B builds
-__global__ __launch_bounds__(256) void gen_fwd_kernel(const HopParams p) {
-    const uint32_t N = p.n_generic;
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t hl = blockIdx.y;
-    const uint32_t ch = blockIdx.z;
-    const int64_t hop = p.hop_first + hl;
-    GF xc = (GF)p.x + (size_t)ch * p.in_stride;
-    GF xt = (GF)p.xtail + (size_t)ch * p.tail_stride;
-    GF src = (hop >= p.tail_hop_first) ? xt + (hop * (int64_t)p.step - p.tail_origin)
-                                       : xc + (hop * (int64_t)p.step - p.in_origin);
-    GF win = (GF)p.window;
-    GV2 tw = (GV2)p.tw_generic;
-    if (k >= N) return;
-    float ax = 0.f, ay = 0.f;
-    uint32_t idx = 0;
-    for (uint32_t n = 0; n < N; ++n) {
-        const float a = src[n] * win[n];  // (src/fft.rs:51-55)
-        const float2 w = ldg2(tw + idx);
-        ax = fmaf(a, w.x, ax);
-        ay = fmaf(a, w.y, ay);
-        idx += k;
-        if (idx >= N) idx -= N;
-    }
-    stg2((GV2W)p.spec + ((size_t)ch * p.hop_count + (size_t)hl) * N + k, make_float2(ax, ay));
-}
-#endif
 // magnitudes x phasors in place on all N bins (between the two transforms)
 __global__ __launch_bounds__(256) void gen_phase_kernel(const HopParams p) {
     const uint32_t N = p.n_generic, half = N / 2;
@@ -132,28 +104,8 @@ __global__ __launch_bounds__(256) void gen_phase_kernel(const HopParams p) {
     sincosf(th, &sn, &cs);
     stg2(z, make_float2(m * cs, m * sn));  // src/fft.rs:65-68
 }
-#if !RC_BLUESTEIN
-__global__ __launch_bounds__(256) void gen_inv_kernel(const HopParams p) {
-    const uint32_t N = p.n_generic;
-    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t hl = blockIdx.y;
-    const uint32_t ch = blockIdx.z;
-    if (n >= N) return;
-    GV2 z = (GV2)p.spec + ((size_t)ch * p.hop_count + (size_t)hl) * N;
-    GV2 tw = (GV2)p.tw_generic;
-    float acc = 0.f;
-    uint32_t idx = 0;
-    for (uint32_t k = 0; k < N; ++k) {
-        const float2 Z = ldg2(z + k), w = ldg2(tw + idx);
-        acc = fmaf(Z.x, w.x, fmaf(Z.y, w.y, acc));  // Re(Z conj(w)), w = (cos, -sin)
-        idx += n;
-        if (idx >= N) idx -= N;
-    }
-    ((GFW)p.ybuf)[((size_t)ch * p.hop_count + (size_t)hl) * N + n] = acc / (float)N * ((GF)p.window)[n];  // fft.rs:70-73
-}
-#endif
 
-// ---- ... and chirp-z (Bluestein) transforms for the lengths whose packed half fits the LDS (N <= 16384) -----------
+// ---- chirp-z (Bluestein) transforms, one workgroup per hop where the packed half fits the LDS (N <= 16384) ------
 // The window is real and N even: z[n] = x[2n] + i x[2n+1] (M = N/2 points), Z = DFT_M(z) by
 //   n k = (n^2 + k^2 - (k - n)^2) / 2  =>  Z[k] = c[k] sum_n (z[n] c[n]) conj(c)[k - n],  c[n] = exp(-i pi n^2 / M):
 // a circular convolution of length L = 2^l >= 2M - 1 = one DIF FFT_L (natural -> bit-reversed), a pointwise product
@@ -406,12 +358,7 @@ hipError_t launch_gen(int stage, const HopParams &p, hipStream_t s) {
             if (stage == 0) hipLaunchKernelGGL(bluestein_kernel<false>, bgrid, bblock, sizeof(float2) * (size_t)L, s, q);
             else hipLaunchKernelGGL(bluestein_kernel<true>, bgrid, bblock, sizeof(float2) * (size_t)L, s, q);
         } else if (stage == 1) hipLaunchKernelGGL(gen_phase_kernel, grid, block, 0, s, q);
-#if !RC_BLUESTEIN
-        else if (stage == 0) hipLaunchKernelGGL(gen_fwd_kernel, grid, block, 0, s, q);
-        else hipLaunchKernelGGL(gen_inv_kernel, grid, block, 0, s, q);
-#else
         else return hipErrorInvalidValue;  // (the engine builds the chirp-z tables for every such length)
-#endif
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

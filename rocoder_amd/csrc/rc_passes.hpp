@@ -3,9 +3,6 @@
 #pragma once
 #include "rc_dev.hpp"
 
-#ifndef RC_PASS_SQ
-#define RC_PASS_SQ 1
-#endif
 namespace rc {
 namespace {
 
@@ -36,33 +33,26 @@ __device__ __forceinline__ void run_pass(float2 (&v)[G::P], int tid,
     // being hoisted out of the hop loop into live registers
     float2 bases[S_HI - S_LO + 1];
     if (LOR > 0) {
-        if (RC_PASS_SQ) {
-            // TWO table loads per pass (the bases of the finest stage and of the one two below it) instead of five; the
-            // others are squares: base(s - 1) = base(s)^2, two packed instructions, at most two deep from a table value
-            // (each squaring doubles the f32 rounding of its input: four deep cost 3e-6 of the output's RMS on the
-            // large-window spectrum path, two deep stays under 1e-6). A global load inside the hop loop is waited on in
-            // place and retires in order behind the previous hop's output stores.
-            constexpr int NS = S_HI - S_LO + 1;
-            float2 bh = ldg2(wtab + (l << (G::m - 1 - S_HI)));
-            float2 bm = NS > 2 ? ldg2(wtab + (l << (G::m - 1 - (S_HI - 2)))) : bh;
-            opaque(bh);
-            opaque(bm);
-            bases[NS - 1] = bh;
-            if (NS > 2) bases[NS - 3] = bm;
+        // TWO table loads per pass (the bases of the finest stage and of the one two below it) instead of five; the
+        // others are squares: base(s - 1) = base(s)^2, two packed instructions, at most two deep from a table value
+        // (each squaring doubles the f32 rounding of its input: four deep cost 3e-6 of the output's RMS on the
+        // large-window spectrum path, two deep stays under 1e-6). A global load inside the hop loop is waited on in
+        // place and retires in order behind the previous hop's output stores.
+        constexpr int NS = S_HI - S_LO + 1;
+        float2 bh = ldg2(wtab + (l << (G::m - 1 - S_HI)));
+        float2 bm = NS > 2 ? ldg2(wtab + (l << (G::m - 1 - (S_HI - 2)))) : bh;
+        opaque(bh);
+        opaque(bm);
+        bases[NS - 1] = bh;
+        if (NS > 2) bases[NS - 3] = bm;
 #pragma unroll
-            for (int si = NS - 2; si >= 0; --si) {
-                if (NS > 2 && si == NS - 3) continue;  // (loaded)
-                const v2f a = to_v(bases[si + 1]);
-                const v2f t = __builtin_shufflevector(a, a, 0, 0) * a;
-                v2f sq;  // t + a.yy * (-a.y, a.x) = a * a
-                asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]" : "=v"(sq) : "v"(a), "v"(a), "v"(t));
-                bases[si] = to_f2(sq);
-            }
-        } else {
-#pragma unroll
-            for (int si = 0; si <= S_HI - S_LO; ++si) bases[si] = ldg2(wtab + (l << (G::m - 1 - (S_LO + si))));
-#pragma unroll
-            for (int si = 0; si <= S_HI - S_LO; ++si) opaque(bases[si]);
+        for (int si = NS - 2; si >= 0; --si) {
+            if (NS > 2 && si == NS - 3) continue;  // (loaded)
+            const v2f a = to_v(bases[si + 1]);
+            const v2f t = __builtin_shufflevector(a, a, 0, 0) * a;
+            v2f sq;  // t + a.yy * (-a.y, a.x) = a * a
+            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]" : "=v"(sq) : "v"(a), "v"(a), "v"(t));
+            bases[si] = to_f2(sq);
         }
     }
 #pragma unroll
@@ -79,7 +69,6 @@ __device__ __forceinline__ void run_pass(float2 (&v)[G::P], int tid,
             const int c = q0 & (half - 1);
             const int kidx = c * (16 >> r);
             const float2 a = v[q0], b = v[q1];
-#if RC_PK
             // packed (re,im) arithmetic as plain vector code: hipcc emits v_pk_* with op_sel / neg /
             // SGPR-constant operands itself (no inline-asm boundary pads)
             const v2f av = to_v(a), bv = to_v(b);
@@ -123,39 +112,6 @@ __device__ __forceinline__ void run_pass(float2 (&v)[G::P], int tid,
                     v[q1] = to_f2(__builtin_elementwise_fma(av, two, -rv));
                 }
             }
-#else
-            if (LOR == 0 && c == 0) {  // w = 1
-                v[q0] = make_float2(a.x + b.x, a.y + b.y);
-                v[q1] = make_float2(a.x - b.x, a.y - b.y);
-            } else if (LOR == 0 && kidx == 8) {  // w = -i
-                if (!INV) {
-                    v[q0] = make_float2(a.x + b.x, a.y + b.y);
-                    const float dx = a.x - b.x, dy = a.y - b.y;
-                    v[q1] = make_float2(dy, -dx);  // d * (-i)
-                } else {
-                    const float tx = -b.y, ty = b.x;  // (+i) * b
-                    v[q0] = make_float2(a.x + tx, a.y + ty);
-                    v[q1] = make_float2(a.x - tx, a.y - ty);
-                }
-            } else {
-                float2 w;
-                if (c == 0) w = base;
-                else if (LOR == 0) w = make_float2(W32_RE[kidx], W32_IM[kidx]);
-                else if (kidx == 8) w = make_float2(base.y, -base.x);
-                else w = cmul(base, make_float2(W32_RE[kidx], W32_IM[kidx]));
-                if (!INV) {
-                    v[q0] = make_float2(a.x + b.x, a.y + b.y);
-                    const float dx = a.x - b.x, dy = a.y - b.y;
-                    v[q1] = make_float2(dx * w.x - dy * w.y, dx * w.y + dy * w.x);
-                } else {
-                    // a + conj(w) b in 4 FMAs, a - conj(w) b = 2a - (a + conj(w) b) in 2
-                    const float rx = fmaf(w.y, b.y, fmaf(w.x, b.x, a.x));
-                    const float ry = fmaf(-w.y, b.x, fmaf(w.x, b.y, a.y));
-                    v[q0] = make_float2(rx, ry);
-                    v[q1] = make_float2(fmaf(2.f, a.x, -rx), fmaf(2.f, a.y, -ry));
-                }
-            }
-#endif
         }
     }
 }
