@@ -203,7 +203,8 @@ int rc_engine_kernel_times(rc_engine *e, float *ms, size_t cap, size_t *n_out);
 /* ReFFT::forward_fft (src/fft.rs:50-61): host samples[window_len] -> host spectrum (re,im)*N */
 int rc_engine_forward_fft(rc_engine *e, const float *samples, float *out_reim);
 /* ReFFT::resynth (src/fft.rs:42-48) for hop `hop` of `channel` (phase key), no overlap-add:
- * host samples[window_len] -> host out[window_len]. Applies the user kernel if configured. */
+ * host samples[window_len] -> host out[window_len]. Applies the user kernel if configured. A single frame has no
+ * earlier one: a user device kernel with RC_HISTORY reads (0, 0) from every X.past(d > 0) here. */
 int rc_engine_resynth(rc_engine *e, uint32_t channel, uint64_t hop, const float *samples,
                       float *out);
 
@@ -217,6 +218,18 @@ int rc_engine_resynth(rc_engine *e, uint32_t channel, uint64_t hop, const float 
  *   h.time_ms rc_config::kernel_time_ms when non-zero, else the wall clock when the launch was enqueued: one value per
  *             launch, not per hop (the reference reads the clock per hop)
  *   h.param(i) the i-th of up to 16 float params (rc_*_set_device_kernel_params), 0 past n_params
+ * History. A source that says `#define RC_HISTORY D` (D = 0 ... RC_DK_MAX_HISTORY = 8; absent = 0) in front of rc_apply
+ * may also read the ANALYSIS spectra of the D hops before its own, as a stateful apply() of the reference keeps them:
+ *   X.past(d)  hop h.hop - d of the same channel, an rc_spectrum like X (read-only, the same modulo-N indexing);
+ *              X.past(0) is X. Every bin reads (0, 0) where d > RC_HISTORY and where h.hop - d < 0: silence precedes a
+ *              stream (src/stretcher.rs:58-59), and a stateful kernel has seen no call before hop 0.
+ *   h.history  the declared D
+ * No d and no index leaves the launch's spectrum block. A larger D does not compile (the error names RC_HISTORY). Earlier
+ * OUTPUTS (feedback) and other channels cannot be read. The depth travels inside the code object (the size of its symbol
+ * rc_user_dk_history is D + 1), so loading needs no further argument; a code object without that symbol runs as D = 0.
+ * Every range, streaming batch and rc_multi shard recomputes the D spectra in front of it from the input, so all entry
+ * points equal the offline job; an open stream retains RC_DK_MAX_HISTORY + 1 steps of input behind its next hop, so
+ * that a kernel swapped in mid-stream sees the same past.
  * The engine owns the prelude that defines rc_spectrum / rc_hop and the wrapper kernel rc_user_dk; rc_apply writes only
  * its return value and must terminate (a kernel cannot be preempted). Compiled with --offload-arch=gfx950 -O3 -std=c++17,
  * no fast-math. Diagnostics name rc_user_dk.hip:<line>, or the file a leading `#line 1 "name"` line names. A user device

@@ -479,6 +479,38 @@ static const DkApi &dk_api() {
     return api;
 }
 
+// The history depth a code object declares (RC_HISTORY in its source): the size of its ELF symbol rc_user_dk_history
+// less one, 0 without the symbol. The watcher hands over bytes only, so the log line reads it from them.
+static unsigned dk_history_of(const std::string &code) {
+    const unsigned char *p = (const unsigned char *)code.data();
+    const size_t len = code.size();
+    auto rd = [&](uint64_t off, size_t n) -> uint64_t {
+        uint64_t x = 0;
+        if (off > len || n > len - off) return 0;
+        for (size_t i = 0; i < n; ++i) x |= (uint64_t)p[off + i] << (8 * i);
+        return x;
+    };
+    static const char kHist[] = "rc_user_dk_history";
+    if (len < 64 || memcmp(p, "\x7f" "ELF", 4) != 0 || p[4] != 2 || p[5] != 1) return 0;
+    const uint64_t shoff = rd(40, 8), shnum = rd(60, 2);
+    if (rd(58, 2) != 64 || shoff > len || shnum > (len - shoff) / 64) return 0;
+    for (uint64_t i = 0; i < shnum; ++i) {
+        const uint64_t sh = shoff + i * 64, type = rd(sh + 4, 4), link = rd(sh + 40, 4);
+        if ((type != 2 && type != 11) || rd(sh + 56, 8) != 24 || link >= shnum) continue;
+        const uint64_t off = rd(sh + 24, 8), size = rd(sh + 32, 8);
+        const uint64_t str_off = rd(shoff + link * 64 + 24, 8), str_size = rd(shoff + link * 64 + 32, 8);
+        if (off > len || size > len - off || str_off > len || str_size > len - str_off) continue;
+        for (uint64_t sym = off; sym + 24 <= off + size; sym += 24) {
+            const uint64_t name = rd(sym, 4);
+            if (name < str_size && str_size - name >= sizeof kHist && memcmp(p + str_off + name, kHist, sizeof kHist) == 0) {
+                const uint64_t sz = rd(sym + 16, 8);
+                return sz >= 1 ? (unsigned)(sz - 1) : 0;
+            }
+        }
+    }
+    return 0;
+}
+
 struct DeviceKernelWatcher {
     std::mutex m;
     std::optional<std::string> pending;
@@ -563,7 +595,7 @@ struct Engine {
         if (!dk) return;
         if (auto code = dk->take()) {
             if (dk_api().load(h, code->data(), code->size()) == RC_OK)
-                fprintf(stderr, "INFO Got new device kernel\n");
+                fprintf(stderr, "INFO Got new device kernel (history: %u earlier hops)\n", dk_history_of(*code));
             else
                 fprintf(stderr, "WARN loading the device kernel failed: %s\n", rc_last_error());
         }
@@ -789,6 +821,7 @@ void usage() {
             "        --device-kernel <spec>         On-GPU frequency kernel: gain:<g> | band:<lo>:<hi>:<g_in>:<g_out> | shift:<bins>\n"
             "        --device-kernel-src <file.hip> On-GPU frequency kernel in HIP, recompiled when the file changes: defines\n"
             "                                       __device__ float2 rc_apply(const rc_spectrum &X, uint32_t j, const rc_hop &h)\n"
+            "                                       A source that says #define RC_HISTORY D (D <= 8) also reads X.past(1..D), the D hops before\n"
             "        --dk-params <a,b,...>          Up to 16 floats for --device-kernel-src (h.param(i))\n"
             "        --kernel-threads <n>           Host threads calling --freq-kernel (channels in parallel; needs a re-entrant kernel)\n"
             "        --seed <u64>                   Phase-source seed (the reference uses an unseeded thread_rng)\n"

@@ -160,7 +160,7 @@ int rtc_compile(const char *src, size_t src_len, std::string *code, std::string 
     return rc;
 }
 
-int rtc_check_code_object(const void *code, size_t len, std::string *why) {
+int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32_t *history) {
     const unsigned char *p = (const unsigned char *)code;
     uint64_t v = 0;
     if (!p || len < 64 || std::memcmp(p, "\x7f" "ELF", 4) != 0 || p[4] != 2 /* ELFCLASS64 */ || p[5] != 1 /* LE */) {
@@ -185,7 +185,9 @@ int rtc_check_code_object(const void *code, size_t len, std::string *why) {
         *why = "bad ELF section header table";
         return RC_EINVAL;
     }
-    static const char kSym[] = "rc_user_dk";
+    static const char kSym[] = "rc_user_dk", kHist[] = "rc_user_dk_history";
+    bool found = false;
+    uint64_t hist_size = 1;  // no marker: depth 0
     for (uint64_t i = 0; i < shnum; ++i) {
         const uint64_t sh = shoff + i * 64;
         uint64_t type = 0, off = 0, size = 0, link = 0, entsize = 0;
@@ -203,24 +205,36 @@ int rtc_check_code_object(const void *code, size_t len, std::string *why) {
         for (uint64_t s = off; s + 24 <= off + size; s += 24) {
             uint64_t name = 0;
             rd(p, len, s, 4, &name);
-            if (name < str_size && str_size - name >= sizeof kSym &&
-                std::memcmp(p + str_off + name, kSym, sizeof kSym) == 0)
-                return RC_OK;
+            if (name >= str_size) continue;
+            if (str_size - name >= sizeof kSym && std::memcmp(p + str_off + name, kSym, sizeof kSym) == 0) found = true;
+            if (str_size - name >= sizeof kHist && std::memcmp(p + str_off + name, kHist, sizeof kHist) == 0)
+                rd(p, len, s + 16, 8, &hist_size);  // st_size
         }
     }
-    *why = "the code object defines no rc_user_dk kernel";
-    return RC_EINVAL;
+    if (!found) {
+        *why = "the code object defines no rc_user_dk kernel";
+        return RC_EINVAL;
+    }
+    if (hist_size < 1 || hist_size > DK_MAX_HISTORY + 1) {
+        *why = "the code object declares an RC_HISTORY outside 0 ... " + std::to_string(DK_MAX_HISTORY);
+        return RC_EINVAL;
+    }
+    if (history) *history = (uint32_t)(hist_size - 1);
+    return RC_OK;
 }
 
 struct UserModule {
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
+    uint32_t history = 0;
 };
 
 int rtc_load(const void *code, size_t len, UserModule **out, std::string *why) {
     *out = nullptr;
-    if (int rc = rtc_check_code_object(code, len, why)) return rc;
+    uint32_t history = 0;
+    if (int rc = rtc_check_code_object(code, len, why, &history)) return rc;
     UserModule *m = new UserModule;
+    m->history = history;
     hipError_t e = hipModuleLoadData(&m->mod, code);
     if (e == hipSuccess) {
         e = hipModuleGetFunction(&m->fn, m->mod, "rc_user_dk");
@@ -241,6 +255,8 @@ void rtc_unload(UserModule *m) {
     (void)hipModuleUnload(m->mod);
     delete m;
 }
+
+uint32_t rtc_history(const UserModule *m) { return m ? m->history : 0; }
 
 hipError_t rtc_launch(const UserModule *m, UserDkArgs a, uint64_t rows, hipStream_t s) {
     const uint64_t per_launch = 32768;  // grid.y limit, as launch_dev_kernel

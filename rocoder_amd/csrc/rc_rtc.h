@@ -11,6 +11,7 @@
 namespace rc {
 
 constexpr uint32_t DK_MAX_PARAMS = 16;
+constexpr uint32_t DK_MAX_HISTORY = 8;  // RC_DK_MAX_HISTORY: earlier hops a user device kernel may read (an interface constant)
 
 // Host mirror of the prelude's rc_dk_args (the wrapper kernel's one argument): keep the two in step
 struct UserDkArgs {
@@ -23,8 +24,13 @@ struct UserDkArgs {
     uint32_t n, mask;
     uint32_t ch_first, n_params;
     float params[DK_MAX_PARAMS];
+    // rc_dk_args_history: the argument block of a kernel that declares a history (a kernel without one, and every
+    // code object without the rc_user_dk_history marker, takes the 128 bytes above and never sees these)
+    uint64_t in_rows;
+    uint32_t halo;
+    uint32_t pad_;
 };
-static_assert(sizeof(UserDkArgs) == 128, "rc_dk_args layout");
+static_assert(offsetof(UserDkArgs, in_rows) == 128 && sizeof(UserDkArgs) == 144, "rc_dk_args layout");
 
 // Every function returns an RC_* status and, on failure, a one-line reason in *why.
 
@@ -34,14 +40,17 @@ static_assert(sizeof(UserDkArgs) == 128, "rc_dk_args layout");
 int rtc_compile(const char *src, size_t src_len, std::string *code, std::string *log, std::string *why);
 
 // RC_OK when `code` is an ELF64 AMDGPU code object for gfx950 that defines the symbol rc_user_dk, else RC_EINVAL.
-// Reads nothing outside [code, code + len).
-int rtc_check_code_object(const void *code, size_t len, std::string *why);
+// *history (when given): the depth the object declares, the size of its symbol rc_user_dk_history less one; 0 for an
+// object without that symbol. A size outside 1 ... DK_MAX_HISTORY + 1 is RC_EINVAL. Reads nothing outside
+// [code, code + len).
+int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32_t *history = nullptr);
 
 struct UserModule;
 // hipModuleLoadData + hipModuleGetFunction("rc_user_dk") on the current device (RC_EHIP on failure)
 int rtc_load(const void *code, size_t len, UserModule **out, std::string *why);
 void rtc_unload(UserModule *m);
-// rows = hop spectra of a.n bins; a.row_first is set per launch (rows are chunked below the grid.y limit)
+uint32_t rtc_history(const UserModule *m);  // the depth the loaded object declares
+// rows = hop spectra of a.n bins to write; a.row_first is set per launch (rows are chunked below the grid.y limit)
 hipError_t rtc_launch(const UserModule *m, UserDkArgs a, uint64_t rows, hipStream_t s);
 
 }  // namespace rc

@@ -6,6 +6,11 @@
 //   __device__ float2 rc_apply(const rc_spectrum &X, uint32_t j, const rc_hop &h);   // returns Y[j]
 // X is one hop's N-bin spectrum in natural DFT order; every index is reduced modulo N, so no read leaves the hop, and
 // the user gets no pointer to write through. rc_apply must terminate: the engine cannot preempt a kernel.
+//
+// A source that says `#define RC_HISTORY D` (0 ... RC_DK_MAX_HISTORY; absent = 0) may also read the analysis spectra of
+// the D hops before its own: X.past(d) is hop h.hop - d of the same channel, an rc_spectrum like X. It reads (0, 0)
+// where d > RC_HISTORY and where h.hop - d < 0 (silence precedes a stream). The wrapper records the depth in the code
+// object as the size of the symbol rc_user_dk_history (D + 1 bytes), which is where the loader finds it.
 R"rc_prelude(
 typedef __hip_internal::uint32_t uint32_t;
 typedef __hip_internal::int32_t int32_t;
@@ -33,12 +38,27 @@ struct rc_spectrum {
     uint32_t n;
     uint32_t mask_;
     __device__ float2 operator[](int64_t i) const {
+        if (zero_) return make_float2(0.f, 0.f);
         if (mask_) return p_[(uint64_t)i & mask_];  // powers of two: two's complement makes this i mod n
         if ((uint64_t)i < n) return p_[i];
         int64_t r = i % (int64_t)n;
         if (r < 0) r += n;
         return p_[r];
     }
+    // the spectrum d hops earlier in the same channel; past(0) is this one
+    __device__ rc_spectrum past(uint32_t d) const {
+        rc_spectrum s = *this;
+        if (d > past_) {
+            s.zero_ = true;
+            s.past_ = 0;
+        } else {
+            s.p_ = p_ - (uint64_t)d * n;
+            s.past_ = past_ - d;
+        }
+        return s;
+    }
+    uint32_t past_;  // rows in front of p_ that past() may reach
+    bool zero_;      // a hop outside the declared history or before the stream: every bin reads (0, 0)
 };
 
 // What the hop is: window length, channel, hop index k (the k of rc_phase_key), the launch's time and the params.
@@ -49,7 +69,18 @@ struct rc_hop {
     uint64_t hop;
     uint64_t time_ms;
     uint32_t n_params;
+    uint32_t history;  // the declared RC_HISTORY
     const float *params_;
     __device__ float param(uint32_t i) const { return i < n_params ? params_[i] : 0.f; }
+};
+
+#define RC_DK_MAX_HISTORY 8
+
+// the argument block of a kernel that declares a history (RC_HISTORY > 0; a kernel without one takes rc_dk_args as it
+// is): `in` is then row 0 of [channel][halo + hop_count][n] past channel 0's halo rows. Host mirror: rc::UserDkArgs.
+struct rc_dk_args_history : rc_dk_args {
+    uint64_t in_rows;  // rows of `in` per channel: halo + hop_count
+    uint32_t halo;     // rows of each channel in front of its hop hop_first (hops hop_first - halo ...)
+    uint32_t pad_;
 };
 )rc_prelude"

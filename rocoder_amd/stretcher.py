@@ -95,6 +95,32 @@ def compile_device_kernel(src, name: Optional[str] = None) -> bytes:
                                    log.value.decode(errors="replace"))
 
 
+def device_kernel_history(code: bytes) -> int:
+    """The history depth a code object from compile_device_kernel declares (`#define RC_HISTORY D` in its source: the
+    earlier hops X.past(1..D) that rc_apply reads), 0 for a source without one. Pure Python: the depth is the size of
+    the ELF symbol rc_user_dk_history less one, and a code object without that symbol has depth 0."""
+    import struct
+
+    b = bytes(code)
+    if len(b) < 64 or b[:4] != b"\x7fELF" or b[4] != 2 or b[5] != 1:
+        raise ValueError("not an ELF64 little-endian code object")
+    shoff, = struct.unpack_from("<Q", b, 40)
+    shentsize, shnum = struct.unpack_from("<HH", b, 58)
+    if shentsize != 64 or shoff + shnum * 64 > len(b):
+        raise ValueError("bad ELF section header table")
+    secs = [struct.unpack_from("<IIQQQQIIQQ", b, shoff + i * 64) for i in range(shnum)]
+    for _name, typ, _flags, _addr, off, size, link, _info, _align, ent in secs:
+        if typ not in (2, 11) or ent != 24 or link >= shnum or off + size > len(b):  # SHT_SYMTAB, SHT_DYNSYM
+            continue
+        stroff, strsize = secs[link][4], secs[link][5]
+        strtab = b[stroff:stroff + strsize]
+        for s in range(off, off + size - 23, 24):
+            st_name, _i, _o, _shndx, _value, st_size = struct.unpack_from("<IBBHQQ", b, s)
+            if strtab[st_name:st_name + 19] == b"rc_user_dk_history\0":
+                return max(0, int(st_size) - 1)
+    return 0
+
+
 def _params_array(params):
     vals = [float(v) for v in params]
     return (C.c_float * max(1, len(vals)))(*vals), len(vals)

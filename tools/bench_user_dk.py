@@ -2,6 +2,8 @@
 job (stereo, L = 2 646 000 per channel, window 16384, factor 8), device-resident input and output:
   * a user SHIFT kernel against the curated RC_DK_SHIFT (the same pipeline: analysis -> kernel -> synthesis -> OLA);
   * the README's x2 kernel as a user device kernel (C4 at GPU speed) against the plain stretch (C2);
+  * examples/kernels/blur.hip at RC_HISTORY 1, 3 and 8 (a weighted sum over the hop and the D hops before it) against
+    the x2 kernel of the same run: what reading earlier hops costs;
   * hiprtc compile time: cold (first compile in a fresh process) and warm.
 Wall time per call (median of --reps after one warm-up, the variants interleaved) and the engine's event time of the
 kernel launches. Prints one JSON line.   python tools/bench_user_dk.py [--reps 7]
@@ -59,13 +61,20 @@ def main():
     job = dict(window_len=16384, factor=8.0, channels=2, seed=1)
     variants = {"plain_c2": dict(), "curated_shift": dict(device_kernel=("shift", 7)),
                 "user_shift": dict(src=SHIFT), "user_x2_c4": dict(src=X2)}
+    with open(os.path.join(ROOT, "examples", "kernels", "blur.hip")) as f:
+        blur = f.read()
+    for depth in (1, 3, 8):
+        variants[f"user_blur_d{depth}"] = dict(src=f"#define RC_HISTORY {depth}\n" + blur,
+                                               params=[1.0 / (depth + 1)] * (depth + 1))
     engines, outs = {}, {}
     for name, v in variants.items():
         kw = dict(job)
-        kw.update({k: val for k, val in v.items() if k != "src"})
+        kw.update({k: val for k, val in v.items() if k not in ("src", "params")})
         e = rocoder_amd.Engine(**kw)
         if "src" in v:
             e.set_device_kernel_source(v["src"])
+        if "params" in v:
+            e.set_device_kernel_params(v["params"])
         engines[name] = e
         outs[name] = torch.empty((2, e.output_len(xd.shape[1])), device="cuda")
         e.stretch_tensor(xd, out=outs[name])
