@@ -204,7 +204,8 @@ int rc_engine_kernel_times(rc_engine *e, float *ms, size_t cap, size_t *n_out);
 int rc_engine_forward_fft(rc_engine *e, const float *samples, float *out_reim);
 /* ReFFT::resynth (src/fft.rs:42-48) for hop `hop` of `channel` (phase key), no overlap-add:
  * host samples[window_len] -> host out[window_len]. Applies the user kernel if configured. A single frame has no
- * earlier one: a user device kernel with RC_HISTORY reads (0, 0) from every X.past(d > 0) here. */
+ * earlier one and no other channel: a user device kernel reads (0, 0) from every X.past(d > 0) and from every
+ * X.channel(c != channel) here, whatever it declares. */
 int rc_engine_resynth(rc_engine *e, uint32_t channel, uint64_t hop, const float *samples,
                       float *out);
 
@@ -225,11 +226,37 @@ int rc_engine_resynth(rc_engine *e, uint32_t channel, uint64_t hop, const float 
  *              stream (src/stretcher.rs:58-59), and a stateful kernel has seen no call before hop 0.
  *   h.history  the declared D
  * No d and no index leaves the launch's spectrum block. A larger D does not compile (the error names RC_HISTORY). Earlier
- * OUTPUTS (feedback) and other channels cannot be read. The depth travels inside the code object (the size of its symbol
+ * OUTPUTS (feedback) cannot be read. The depth travels inside the code object (the size of its symbol
  * rc_user_dk_history is D + 1), so loading needs no further argument; a code object without that symbol runs as D = 0.
  * Every range, streaming batch and rc_multi shard recomputes the D spectra in front of it from the input, so all entry
  * points equal the offline job; an open stream retains RC_DK_MAX_HISTORY + 1 steps of input behind its next hop, so
  * that a kernel swapped in mid-stream sees the same past.
+ * Other channels. A source that says `#define RC_CROSS_CHANNEL 1` in front of rc_apply (absent or 0: off; any other
+ * value does not compile, the error names RC_CROSS_CHANNEL) may also read the ANALYSIS spectra of every channel of the
+ * job, as a stateful apply() served by the processor's round-robin sees its siblings (src/stretcher_processor.rs:63-70):
+ *   X.channel(c)  hop h.hop of channel c, an rc_spectrum like X; X.channel(h.channel) is X, declared or not. Every bin
+ *                 reads (0, 0) where c >= h.channels and, for another channel, where the source did not declare
+ *                 RC_CROSS_CHANNEL. It composes with the history: X.channel(c).past(d) and X.past(d).channel(c) are both
+ *                 hop h.hop - d of channel c, with the zero rules of past().
+ *   h.channels    rc_config::channels under the declaration, 0 without it (the unchanged 128-byte argument block of an
+ *                 undeclared kernel has no room for it)
+ * No c leaves the launch's spectrum block. The declaration travels inside the code object (the symbol
+ * rc_user_dk_channels); one without it runs as undeclared, with the argument block, launches and scratch it always had.
+ * While a declared kernel is loaded, a call for part of the channels (a range, an rc_multi shard) still runs the forward
+ * transforms of ALL channels over its hops and holds their spectra, up to rc_config::channels times the analysis work
+ * and spectrum scratch of the asked part; a whole-job call analyses every channel anyway. d_in of the range form holds
+ * every channel already; rc_multi sends every channel's input span to each shard. Streams, whose channels need not be
+ * equally long or equally far:
+ *   - hop k of a CLOSED channel reads zeros past its end (src/stretcher.rs:129-132), also when another channel reads it;
+ *   - rc_engine_next_window(c) returns RC_WOULD_BLOCK unless every channel that is still OPEN holds the input of all
+ *     hops of that window;
+ *   - every channel's input is kept back to what the SLOWEST unfinished channel's next hop can still read (its next hop
+ *     - 1 - RC_DK_MAX_HISTORY): a host that pulls one channel far ahead of another holds that much more input, as the
+ *     reference's unbounded input channel would (src/main.rs:133);
+ *   - a declared kernel is loaded on a stream only while all channels stand at the same next window (before the first
+ *     window, or between rounds of the processor's loop): else RC_EINVAL, and the previous kernel stays;
+ *   - channels that are all closed, equally long and at the same window are computed together and need no extra analysis.
+ * With these rules every entry point equals the offline job bit for bit.
  * The engine owns the prelude that defines rc_spectrum / rc_hop and the wrapper kernel rc_user_dk; rc_apply writes only
  * its return value and must terminate (a kernel cannot be preempted). Compiled with --offload-arch=gfx950 -O3 -std=c++17,
  * no fast-math. Diagnostics name rc_user_dk.hip:<line>, or the file a leading `#line 1 "name"` line names. A user device

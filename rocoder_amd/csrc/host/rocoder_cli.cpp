@@ -480,8 +480,9 @@ static const DkApi &dk_api() {
 }
 
 // The history depth a code object declares (RC_HISTORY in its source): the size of its ELF symbol rc_user_dk_history
-// less one, 0 without the symbol. The watcher hands over bytes only, so the log line reads it from them.
-static unsigned dk_history_of(const std::string &code) {
+// less one, 0 without the symbol. The watcher hands over bytes only, so the log line reads it from them. With `cross`:
+// whether the object declares RC_CROSS_CHANNEL (defines the symbol rc_user_dk_channels) instead.
+static unsigned dk_history_of(const std::string &code, bool cross = false) {
     const unsigned char *p = (const unsigned char *)code.data();
     const size_t len = code.size();
     auto rd = [&](uint64_t off, size_t n) -> uint64_t {
@@ -490,7 +491,7 @@ static unsigned dk_history_of(const std::string &code) {
         for (size_t i = 0; i < n; ++i) x |= (uint64_t)p[off + i] << (8 * i);
         return x;
     };
-    static const char kHist[] = "rc_user_dk_history";
+    static const char kHist[] = "rc_user_dk_history", kChan[] = "rc_user_dk_channels";
     if (len < 64 || memcmp(p, "\x7f" "ELF", 4) != 0 || p[4] != 2 || p[5] != 1) return 0;
     const uint64_t shoff = rd(40, 8), shnum = rd(60, 2);
     if (rd(58, 2) != 64 || shoff > len || shnum > (len - shoff) / 64) return 0;
@@ -502,6 +503,11 @@ static unsigned dk_history_of(const std::string &code) {
         if (off > len || size > len - off || str_off > len || str_size > len - str_off) continue;
         for (uint64_t sym = off; sym + 24 <= off + size; sym += 24) {
             const uint64_t name = rd(sym, 4);
+            if (cross) {
+                if (name < str_size && str_size - name >= sizeof kChan && memcmp(p + str_off + name, kChan, sizeof kChan) == 0)
+                    return 1;
+                continue;
+            }
             if (name < str_size && str_size - name >= sizeof kHist && memcmp(p + str_off + name, kHist, sizeof kHist) == 0) {
                 const uint64_t sz = rd(sym + 16, 8);
                 return sz >= 1 ? (unsigned)(sz - 1) : 0;
@@ -590,15 +596,45 @@ struct Engine {
     rc_engine *h = nullptr;
     std::mutex m;  // one thread at a time per handle
     DeviceKernelWatcher *dk = nullptr;  // --device-kernel-src
-    // between two windows, with m held: a device kernel the watcher compiled since the last window
+    std::optional<std::string> dk_held;  // a kernel that reads the other channels, waiting for the top of a round
+    // between two windows, with m held: a device kernel the watcher compiled since the last window. One that declares
+    // RC_CROSS_CHANNEL loads only while all channels stand at the same window: it is kept until the round is over.
     void poll_device_kernel() {
         if (!dk) return;
-        if (auto code = dk->take()) {
-            if (dk_api().load(h, code->data(), code->size()) == RC_OK)
-                fprintf(stderr, "INFO Got new device kernel (history: %u earlier hops)\n", dk_history_of(*code));
-            else
-                fprintf(stderr, "WARN loading the device kernel failed: %s\n", rc_last_error());
-        }
+        auto code = dk->take();
+        if (code) dk_held.reset();  // (a newer source replaces one still waiting)
+        else if (dk_held) code = std::move(dk_held), dk_held.reset();
+        if (!code) return;
+        const bool cross = dk_history_of(*code, true) != 0;
+        const int rc = dk_api().load(h, code->data(), code->size());
+        if (rc == RC_OK)
+            fprintf(stderr, "INFO Got new device kernel (history: %u earlier hops%s)\n", dk_history_of(*code),
+                    cross ? ", reads the other channels" : "");
+        else if (rc == RC_EINVAL && cross)
+            dk_held = std::move(code);
+        else
+            fprintf(stderr, "WARN loading the device kernel failed: %s\n", rc_last_error());
+    }
+    // What main queued for each channel and has not reached the engine yet (the Sender side of stretcher.rs:125). It
+    // lives here, not in the channel's Stretcher, because a device kernel that reads the other channels makes a
+    // window of one channel wait for the input of all of them, and one thread walks the Stretchers in turn.
+    struct Feed {
+        std::deque<std::vector<float>> input;
+        bool input_closed = false;
+    };
+    std::vector<Feed> feed;
+    // with m held: the next queued block of the channel goes to the engine; false when nothing is queued
+    bool feed_channel(uint32_t c) {
+        Feed &f = feed[c];
+        if (f.input.empty()) return false;
+        rc_engine_push_input(h, c, f.input.front().data(), f.input.front().size());
+        f.input.pop_front();
+        // file input: main queued the whole channel and dropped its sender before the processor started
+        // (main.rs:148-150), so an empty queue IS the disconnect. Telling the engine now instead of at the
+        // next shortfall lets it batch ahead (an open channel is computed one queue-bound at a time);
+        // the windows are the same either way
+        if (f.input.empty() && f.input_closed) rc_engine_close_input(h, c);
+        return true;
     }
     ~Engine() { rc_engine_destroy(h); }
 };
@@ -608,8 +644,6 @@ struct Stretcher {
     uint32_t channel;
     rc_params par;
     // the Receiver<Vec<f32>> side: main sends the whole channel as one chunk (main.rs:148)
-    std::deque<std::vector<float>> input;
-    bool input_closed = false;
 
     bool is_done() {  // stretcher.rs:78-80
         std::lock_guard<std::mutex> lk(eng->m);
@@ -632,17 +666,12 @@ struct Stretcher {
             }
             if (rc != RC_WOULD_BLOCK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
             std::lock_guard<std::mutex> lk(eng->m);  // self.input.recv(), stretcher.rs:125
-            if (!input.empty()) {
-                rc_engine_push_input(eng->h, channel, input.front().data(), input.front().size());
-                input.pop_front();
-                // file input: main queued the whole channel and dropped its sender before the processor started
-                // (main.rs:148-150), so an empty queue IS the disconnect. Telling the engine now instead of at the
-                // next shortfall lets it batch ahead (an open channel is computed one queue-bound at a time);
-                // the windows are the same either way
-                if (input.empty() && input_closed) rc_engine_close_input(eng->h, channel);
-            } else {
-                rc_engine_close_input(eng->h, channel);  // Err(_): Sender dropped, stretcher.rs:129-132
-            }
+            if (eng->feed_channel(channel)) continue;
+            // nothing of its own is left: a kernel that reads the other channels waits for THEIR input, which their
+            // own next_window would bring only after this one returns
+            bool fed = false;
+            for (uint32_t c = 0; c < eng->feed.size(); ++c) fed = (c != channel && eng->feed_channel(c)) || fed;
+            if (!fed) rc_engine_close_input(eng->h, channel);  // Err(_): Sender dropped, stretcher.rs:129-132
         }
     }
 };
@@ -822,6 +851,7 @@ void usage() {
             "        --device-kernel-src <file.hip> On-GPU frequency kernel in HIP, recompiled when the file changes: defines\n"
             "                                       __device__ float2 rc_apply(const rc_spectrum &X, uint32_t j, const rc_hop &h)\n"
             "                                       A source that says #define RC_HISTORY D (D <= 8) also reads X.past(1..D), the D hops before\n"
+            "                                       One that says #define RC_CROSS_CHANNEL 1 also reads X.channel(c), the other channels' spectra\n"
             "        --dk-params <a,b,...>          Up to 16 floats for --device-kernel-src (h.param(i))\n"
             "        --kernel-threads <n>           Host threads calling --freq-kernel (channels in parallel; needs a re-entrant kernel)\n"
             "        --seed <u64>                   Phase-source seed (the reference uses an unseeded thread_rng)\n"
@@ -1023,6 +1053,7 @@ int run(int argc, char **argv) {
     lap("engine create");
 
     // one Stretcher per channel, fed the whole channel as one chunk (src/main.rs:133-153)
+    eng->feed.resize(spec.channels);
     std::vector<Stretcher> stretchers;
     for (uint32_t c = 0; c < spec.channels; ++c) {
         Stretcher s;
@@ -1030,8 +1061,8 @@ int run(int argc, char **argv) {
         s.eng = eng;
         s.channel = c;
         rc_engine_get_params(eng->h, &s.par);
-        s.input.push_back(std::move(audio.data[c]));
-        s.input_closed = true;  // nothing else will be sent
+        eng->feed[c].input.push_back(std::move(audio.data[c]));
+        eng->feed[c].input_closed = true;  // nothing else will be sent
         stretchers.push_back(std::move(s));
     }
     const size_t expected_total_samples = (size_t)((float)total_samples_len * o.factor);  // main.rs:154

@@ -7,7 +7,7 @@
 ROOT := ../../..
 CXX  ?= g++
 COMMON := -g -O1 -std=c++17 -Wall -fno-omit-frame-pointer rocoder_cli.cpp -ldl -lpthread
-all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../bin/engine_tsan ../../bin/engine_dk_asan
+all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../bin/engine_tsan ../../bin/engine_dk_asan ../../bin/engine_xch_asan
 ../../bin/rocoder_asan: rocoder_cli.cpp $(ROOT)/include/rocoder_hip.h ../../librocoder_hip.so
 	mkdir -p ../../bin
 	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(COMMON) -o $@ -L../.. -lrocoder_hip \
@@ -36,4 +36,9 @@ ENGINE_DK_SRC := $(filter-out %/engine_host_driver.cpp,$(ENGINE_SRC)) $(ROOT)/te
 ../../bin/engine_dk_asan: $(ENGINE_DK_SRC) ../rc_kernels.h ../rc_long.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
 	mkdir -p ../../bin
 	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(ENGINE_FLAGS) $(ENGINE_DK_SRC) -o $@ -lpthread -ldl
+# ... and by tests/c/engine_host_driver_xch.cpp: a user device kernel that reads the other channels loaded
+ENGINE_XCH_SRC := $(filter-out %/engine_host_driver.cpp,$(ENGINE_SRC)) $(ROOT)/tests/c/engine_host_driver_xch.cpp
+../../bin/engine_xch_asan: $(ENGINE_XCH_SRC) ../rc_kernels.h ../rc_long.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
+	mkdir -p ../../bin
+	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(ENGINE_FLAGS) $(ENGINE_XCH_SRC) -o $@ -lpthread -ldl
 .PHONY: all

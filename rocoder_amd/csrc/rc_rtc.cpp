@@ -160,7 +160,7 @@ int rtc_compile(const char *src, size_t src_len, std::string *code, std::string 
     return rc;
 }
 
-int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32_t *history) {
+int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32_t *history, bool *cross) {
     const unsigned char *p = (const unsigned char *)code;
     uint64_t v = 0;
     if (!p || len < 64 || std::memcmp(p, "\x7f" "ELF", 4) != 0 || p[4] != 2 /* ELFCLASS64 */ || p[5] != 1 /* LE */) {
@@ -185,8 +185,8 @@ int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32
         *why = "bad ELF section header table";
         return RC_EINVAL;
     }
-    static const char kSym[] = "rc_user_dk", kHist[] = "rc_user_dk_history";
-    bool found = false;
+    static const char kSym[] = "rc_user_dk", kHist[] = "rc_user_dk_history", kChan[] = "rc_user_dk_channels";
+    bool found = false, chan = false;
     uint64_t hist_size = 1;  // no marker: depth 0
     for (uint64_t i = 0; i < shnum; ++i) {
         const uint64_t sh = shoff + i * 64;
@@ -209,6 +209,7 @@ int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32
             if (str_size - name >= sizeof kSym && std::memcmp(p + str_off + name, kSym, sizeof kSym) == 0) found = true;
             if (str_size - name >= sizeof kHist && std::memcmp(p + str_off + name, kHist, sizeof kHist) == 0)
                 rd(p, len, s + 16, 8, &hist_size);  // st_size
+            if (str_size - name >= sizeof kChan && std::memcmp(p + str_off + name, kChan, sizeof kChan) == 0) chan = true;
         }
     }
     if (!found) {
@@ -220,6 +221,7 @@ int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32
         return RC_EINVAL;
     }
     if (history) *history = (uint32_t)(hist_size - 1);
+    if (cross) *cross = chan;
     return RC_OK;
 }
 
@@ -227,14 +229,17 @@ struct UserModule {
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
     uint32_t history = 0;
+    bool cross = false;
 };
 
 int rtc_load(const void *code, size_t len, UserModule **out, std::string *why) {
     *out = nullptr;
     uint32_t history = 0;
-    if (int rc = rtc_check_code_object(code, len, why, &history)) return rc;
+    bool cross = false;
+    if (int rc = rtc_check_code_object(code, len, why, &history, &cross)) return rc;
     UserModule *m = new UserModule;
     m->history = history;
+    m->cross = cross;
     hipError_t e = hipModuleLoadData(&m->mod, code);
     if (e == hipSuccess) {
         e = hipModuleGetFunction(&m->fn, m->mod, "rc_user_dk");
@@ -257,6 +262,7 @@ void rtc_unload(UserModule *m) {
 }
 
 uint32_t rtc_history(const UserModule *m) { return m ? m->history : 0; }
+bool rtc_cross(const UserModule *m) { return m && m->cross; }
 
 hipError_t rtc_launch(const UserModule *m, UserDkArgs a, uint64_t rows, hipStream_t s) {
     const uint64_t per_launch = 32768;  // grid.y limit, as launch_dev_kernel

@@ -29,8 +29,15 @@ struct UserDkArgs {
     uint64_t in_rows;
     uint32_t halo;
     uint32_t pad_;
+    // rc_dk_args_channels: what a kernel that declares RC_CROSS_CHANNEL takes on top (its input block holds channels
+    // [in_ch_first, in_ch_first + in_ch_count) of the job; nobody else sees these)
+    uint32_t channels;
+    uint32_t in_ch_first;
+    uint32_t in_ch_count;
+    uint32_t pad2_;
 };
-static_assert(offsetof(UserDkArgs, in_rows) == 128 && sizeof(UserDkArgs) == 144, "rc_dk_args layout");
+static_assert(offsetof(UserDkArgs, in_rows) == 128 && offsetof(UserDkArgs, channels) == 144 && sizeof(UserDkArgs) == 160,
+              "rc_dk_args layout");
 
 // Every function returns an RC_* status and, on failure, a one-line reason in *why.
 
@@ -42,14 +49,17 @@ int rtc_compile(const char *src, size_t src_len, std::string *code, std::string 
 // RC_OK when `code` is an ELF64 AMDGPU code object for gfx950 that defines the symbol rc_user_dk, else RC_EINVAL.
 // *history (when given): the depth the object declares, the size of its symbol rc_user_dk_history less one; 0 for an
 // object without that symbol. A size outside 1 ... DK_MAX_HISTORY + 1 is RC_EINVAL. Reads nothing outside
-// [code, code + len).
-int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32_t *history = nullptr);
+// [code, code + len). *cross (when given): whether the object declares RC_CROSS_CHANNEL, i.e. defines the symbol
+// rc_user_dk_channels.
+int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32_t *history = nullptr,
+                          bool *cross = nullptr);
 
 struct UserModule;
 // hipModuleLoadData + hipModuleGetFunction("rc_user_dk") on the current device (RC_EHIP on failure)
 int rtc_load(const void *code, size_t len, UserModule **out, std::string *why);
 void rtc_unload(UserModule *m);
 uint32_t rtc_history(const UserModule *m);  // the depth the loaded object declares
+bool rtc_cross(const UserModule *m);        // whether it declares RC_CROSS_CHANNEL
 // rows = hop spectra of a.n bins to write; a.row_first is set per launch (rows are chunked below the grid.y limit)
 hipError_t rtc_launch(const UserModule *m, UserDkArgs a, uint64_t rows, hipStream_t s);
 

@@ -11,6 +11,13 @@
 // the D hops before its own: X.past(d) is hop h.hop - d of the same channel, an rc_spectrum like X. It reads (0, 0)
 // where d > RC_HISTORY and where h.hop - d < 0 (silence precedes a stream). The wrapper records the depth in the code
 // object as the size of the symbol rc_user_dk_history (D + 1 bytes), which is where the loader finds it.
+//
+// A source that says `#define RC_CROSS_CHANNEL 1` (absent or 0: off) may read the analysis spectra of the job's other
+// channels: X.channel(c) is hop h.hop of channel c, an rc_spectrum like X, and composes with past() in either order.
+// X.channel(h.channel) is X itself, declared or not. Every bin reads (0, 0) where c >= h.channels and, for another
+// channel, where the source did not declare RC_CROSS_CHANNEL. h.channels is rc_config::channels under the declaration and
+// 0 without it: the 128-byte argument block of an undeclared kernel is unchanged and has no room for it. The wrapper
+// records the declaration as the symbol rc_user_dk_channels, which the loader looks for.
 R"rc_prelude(
 typedef __hip_internal::uint32_t uint32_t;
 typedef __hip_internal::int32_t int32_t;
@@ -57,8 +64,23 @@ struct rc_spectrum {
         }
         return s;
     }
+    // the same hop of channel c of the job; channel(h.channel) is this one
+    __device__ rc_spectrum channel(uint32_t c) const {
+        rc_spectrum s = *this;
+        if (c == ch_) return s;
+        if (c - ch_lo_ >= ch_n_) {
+            s.zero_ = true;
+        } else {
+            s.p_ = p_ + ((int64_t)c - (int64_t)ch_) * (int64_t)((uint64_t)ch_rows_ * n);
+            s.ch_ = c;
+        }
+        return s;
+    }
     uint32_t past_;  // rows in front of p_ that past() may reach
-    bool zero_;      // a hop outside the declared history or before the stream: every bin reads (0, 0)
+    bool zero_;      // a hop outside the declared history or before the stream, a channel outside the block: (0, 0)
+    uint32_t ch_;            // the channel p_ belongs to
+    uint32_t ch_lo_, ch_n_;  // channels [ch_lo_, ch_lo_ + ch_n_) lie in the block (undeclared: none but ch_)
+    uint32_t ch_rows_;       // rows from one channel of the block to the next
 };
 
 // What the hop is: window length, channel, hop index k (the k of rc_phase_key), the launch's time and the params.
@@ -70,6 +92,7 @@ struct rc_hop {
     uint64_t time_ms;
     uint32_t n_params;
     uint32_t history;  // the declared RC_HISTORY
+    uint32_t channels;  // rc_config::channels under RC_CROSS_CHANNEL, else 0
     const float *params_;
     __device__ float param(uint32_t i) const { return i < n_params ? params_[i] : 0.f; }
 };
@@ -82,5 +105,15 @@ struct rc_dk_args_history : rc_dk_args {
     uint64_t in_rows;  // rows of `in` per channel: halo + hop_count
     uint32_t halo;     // rows of each channel in front of its hop hop_first (hops hop_first - halo ...)
     uint32_t pad_;
+};
+
+// the argument block of a kernel that declares RC_CROSS_CHANNEL (with or without a history): `in` is hop hop_first of
+// the block's first channel in [in_ch_count channels][halo + hop_count][n], which holds channels in_ch_first ... of the
+// job, while the output rows are those of ch_first ... only. Host mirror: rc::UserDkArgs.
+struct rc_dk_args_channels : rc_dk_args_history {
+    uint32_t channels;     // rc_config::channels
+    uint32_t in_ch_first;  // first channel of the input block
+    uint32_t in_ch_count;  // channels in the input block (a single frame: 1, its own)
+    uint32_t pad2_;
 };
 )rc_prelude"

@@ -1,6 +1,7 @@
 // The wrapper kernel of a user device kernel (rc_dk_compile), compiled after the user's source: one thread per output
 // bin, grid (ceil(n / 256), rows). It writes out of place, so rc_apply may gather from any bin of its hop and of the
-// RC_HISTORY hops before it: rows [halo of the channel][its hops] of the input block, never outside it.
+// RC_HISTORY hops before it: rows [halo of the channel][its hops] of the input block, never outside it. Under
+// RC_CROSS_CHANNEL the block holds every channel of the job and X.channel(c) steps from one channel's rows to another's.
 R"rc_wrapper(
 #line 1 "rc_user_dk_wrapper"
 #ifndef RC_HISTORY
@@ -10,7 +11,15 @@ static_assert((RC_HISTORY) >= 0 && (RC_HISTORY) <= RC_DK_MAX_HISTORY,
               "RC_HISTORY must be 0 ... RC_DK_MAX_HISTORY (8) earlier hops");
 // the declared depth, for the loader: a symbol of RC_HISTORY + 1 bytes
 extern "C" __device__ __attribute__((used)) char rc_user_dk_history[(RC_HISTORY) + 1] = {};
-#if (RC_HISTORY) > 0
+#ifndef RC_CROSS_CHANNEL
+#define RC_CROSS_CHANNEL 0
+#endif
+static_assert((RC_CROSS_CHANNEL) == 0 || (RC_CROSS_CHANNEL) == 1, "RC_CROSS_CHANNEL must be 0 or 1");
+#if (RC_CROSS_CHANNEL)
+// the declaration, for the loader: the presence of this symbol
+extern "C" __device__ __attribute__((used)) char rc_user_dk_channels[1] = {};
+typedef rc_dk_args_channels rc_dk_args_t;
+#elif (RC_HISTORY) > 0
 typedef rc_dk_args_history rc_dk_args_t;
 #else
 typedef rc_dk_args rc_dk_args_t;
@@ -25,9 +34,25 @@ extern "C" __global__ __launch_bounds__(256) void rc_user_dk(const rc_dk_args_t 
     X.n = a.n;
     X.mask_ = a.mask;
     X.zero_ = false;
-#if (RC_HISTORY) > 0
+    const uint32_t channel = a.ch_first + (uint32_t)(r / a.hop_count);
+    X.ch_ = channel;
+#if (RC_CROSS_CHANNEL)
+    X.ch_lo_ = a.in_ch_first;
+    X.ch_n_ = a.in_ch_count;
+    X.ch_rows_ = (uint32_t)a.in_rows;
+#else
+    X.ch_lo_ = channel;
+    X.ch_n_ = 1;
+    X.ch_rows_ = 0;
+#endif
+#if (RC_HISTORY) > 0 || (RC_CROSS_CHANNEL)
     // row r of the output is row ch * in_rows + hl of the input, with a.halo rows of the channel in front of hl = 0
-    const uint64_t ch = r / a.hop_count, hl = r % a.hop_count;
+#if (RC_CROSS_CHANNEL)
+    const uint64_t ch = channel - a.in_ch_first;  // (the block holds more channels than the rows asked for)
+#else
+    const uint64_t ch = r / a.hop_count;
+#endif
+    const uint64_t hl = r % a.hop_count;
     const uint64_t behind = a.halo + hl;
     X.p_ = a.in + (ch * a.in_rows + hl) * a.n;
     X.past_ = (uint32_t)(behind < (uint64_t)(RC_HISTORY) ? behind : (uint64_t)(RC_HISTORY));
@@ -38,7 +63,12 @@ extern "C" __global__ __launch_bounds__(256) void rc_user_dk(const rc_dk_args_t 
 #endif
     rc_hop h;
     h.n = a.n;
-    h.channel = a.ch_first + (uint32_t)(r / a.hop_count);
+    h.channel = channel;
+#if (RC_CROSS_CHANNEL)
+    h.channels = a.channels;
+#else
+    h.channels = 0;
+#endif
     h.hop = (uint64_t)k;
     h.history = (RC_HISTORY);
     h.time_ms = a.time_ms;

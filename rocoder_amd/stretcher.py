@@ -95,6 +95,35 @@ def compile_device_kernel(src, name: Optional[str] = None) -> bytes:
                                    log.value.decode(errors="replace"))
 
 
+def _code_object_symbols(code: bytes):
+    """(name, size) of every symbol of an ELF64 little-endian code object."""
+    import struct
+
+    b = bytes(code)
+    if len(b) < 64 or b[:4] != b"\x7fELF" or b[4] != 2 or b[5] != 1:
+        raise ValueError("not an ELF64 little-endian code object")
+    shoff, = struct.unpack_from("<Q", b, 40)
+    shentsize, shnum = struct.unpack_from("<HH", b, 58)
+    if shentsize != 64 or shoff + shnum * 64 > len(b):
+        raise ValueError("bad ELF section header table")
+    secs = [struct.unpack_from("<IIQQQQIIQQ", b, shoff + i * 64) for i in range(shnum)]
+    for _name, typ, _flags, _addr, off, size, link, _info, _align, ent in secs:
+        if typ not in (2, 11) or ent != 24 or link >= shnum or off + size > len(b):  # SHT_SYMTAB, SHT_DYNSYM
+            continue
+        stroff, strsize = secs[link][4], secs[link][5]
+        strtab = b[stroff:stroff + strsize]
+        for s in range(off, off + size - 23, 24):
+            st_name, _i, _o, _shndx, _value, st_size = struct.unpack_from("<IBBHQQ", b, s)
+            end = strtab.find(b"\0", st_name)
+            yield strtab[st_name:end if end >= 0 else None], int(st_size)
+
+
+def device_kernel_cross_channel(code: bytes) -> bool:
+    """Whether a code object from compile_device_kernel declares `#define RC_CROSS_CHANNEL 1` (rc_apply reads the other
+    channels' spectra through X.channel(c)). Pure Python: the declaration is the ELF symbol rc_user_dk_channels."""
+    return any(name == b"rc_user_dk_channels" for name, _size in _code_object_symbols(code))
+
+
 def device_kernel_history(code: bytes) -> int:
     """The history depth a code object from compile_device_kernel declares (`#define RC_HISTORY D` in its source: the
     earlier hops X.past(1..D) that rc_apply reads), 0 for a source without one. Pure Python: the depth is the size of
