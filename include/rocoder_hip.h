@@ -163,6 +163,28 @@ size_t rc_engine_channel_bound(const rc_engine *e);
  * eight copy threads. Blocking: out[c] is complete on return. */
 int rc_engine_stretch_host(rc_engine *e, const float *const *in, size_t in_len, float *const *out,
                            size_t out_cap, size_t *out_len);
+/* The same job on interleaved PCM frames, as a WAV data chunk, a socket or the reference's reader deliver them
+ * (src/audio_files.rs:30-49,159-188), with interleaved f32 frames back, as its writer takes them (src/audio_files.rs:
+ * 203-226). `frames` holds n_frames x channels samples, frame-major and little endian, at ANY byte alignment (a data
+ * chunk sits wherever its header ends); out_frames receives rc_offline_output_len(cfg, n_frames) frames of `channels`
+ * floats. Both format changes run as kernels on the device inside the upload / compute / download pipeline of
+ * rc_engine_stretch_host: the raw bytes cross PCIe (an int16 source at half the size of its floats), and the output
+ * equals rc_engine_stretch_host on the decoded rows bit for bit. Sample -> float, the reader's formulas:
+ *   RC_PCM_U8   n = byte - 128, then n / 127           (hound's u8 -> i8, src/audio.rs:16-29)
+ *   RC_PCM_I16  n / 32767
+ *   RC_PCM_I24  3 bytes little endian, sign-extended, n / 8388608
+ *   RC_PCM_I32  n / 2147483647
+ *   RC_PCM_F32  the bits as they are
+ * each (float)n / K one correctly rounded f32 division. RC_EINVAL: a null pointer, a format outside 1 ... 5;
+ * RC_ECAPACITY: out_cap_frames too small. n_frames == 0 is valid (what rc_engine_stretch_host gives for in_len == 0).
+ * Pageable and page-locked memory both work on either side. Blocking: out_frames is complete on return. */
+#define RC_PCM_U8 1
+#define RC_PCM_I16 2
+#define RC_PCM_I24 3
+#define RC_PCM_I32 4
+#define RC_PCM_F32 5
+int rc_engine_stretch_frames(rc_engine *e, const void *frames, size_t n_frames, uint32_t format,
+                             float *out_frames, size_t out_cap_frames, size_t *out_frames_len);
 /* Page-locked host memory for the host-form calls (the `Vec<f32>` a Rust host would otherwise hand over, src/main.rs:
  * 148, src/audio.rs:152-172): rows allocated here cross PCIe without a staging copy. rc_host_free(NULL) is a no-op.
  * RC_ENODEVICE without a GPU, RC_ENOMEM when the pages cannot be locked. */

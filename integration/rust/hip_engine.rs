@@ -23,6 +23,12 @@ pub const RC_DK_NONE: u32 = 0;
 pub const RC_DK_GAIN: u32 = 1;
 pub const RC_DK_BAND: u32 = 2;
 pub const RC_DK_SHIFT: u32 = 3;
+// rc_engine_stretch_frames: the sample format of interleaved PCM frames
+pub const RC_PCM_U8: u32 = 1;
+pub const RC_PCM_I16: u32 = 2;
+pub const RC_PCM_I24: u32 = 3;
+pub const RC_PCM_I32: u32 = 4;
+pub const RC_PCM_F32: u32 = 5;
 
 /// `rc_config`: the arguments of `Stretcher::new` (src/stretcher.rs:30-39) for all channels of a job.
 #[repr(C)]
@@ -73,6 +79,8 @@ extern "C" {
     pub fn rc_engine_channel_bound(e: *const RcEngine) -> usize;
     pub fn rc_engine_stretch_host(e: *mut RcEngine, inp: *const *const f32, in_len: usize,
                                   out: *const *mut f32, out_cap: usize, out_len: *mut usize) -> c_int;
+    pub fn rc_engine_stretch_frames(e: *mut RcEngine, frames: *const c_void, n_frames: usize, format: u32,
+                                    out_frames: *mut f32, out_cap_frames: usize, out_frames_len: *mut usize) -> c_int;
     pub fn rc_host_alloc(bytes: usize, out: *mut *mut c_void) -> c_int;   // page-locked rows: no staging copy
     pub fn rc_host_free(p: *mut c_void) -> c_int;
     pub fn rc_engine_stretch_device(e: *mut RcEngine, d_in: *const f32, in_stride: usize, in_len: usize,

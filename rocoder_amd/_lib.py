@@ -50,6 +50,10 @@ class rc_config(C.Structure):
 
 
 RC_DK_NONE, RC_DK_GAIN, RC_DK_BAND, RC_DK_SHIFT = 0, 1, 2, 3
+# rc_engine_stretch_frames: sample formats of interleaved PCM frames, and the bytes one sample takes
+RC_PCM_U8, RC_PCM_I16, RC_PCM_I24, RC_PCM_I32, RC_PCM_F32 = 1, 2, 3, 4, 5
+PCM_FORMATS = {"u8": RC_PCM_U8, "i16": RC_PCM_I16, "i24": RC_PCM_I24, "i32": RC_PCM_I32, "f32": RC_PCM_F32}
+PCM_BYTES = {RC_PCM_U8: 1, RC_PCM_I16: 2, RC_PCM_I24: 3, RC_PCM_I32: 4, RC_PCM_F32: 4}
 
 
 class rc_params(C.Structure):
@@ -100,6 +104,7 @@ SYMBOLS = {
     "rc_engine_channel_bound": (_sz, [_eng]),
     "rc_engine_stretch_host": (C.c_int, [_eng, C.POINTER(_fp), _sz, C.POINTER(_fp), _sz,
                                          C.POINTER(_sz)]),
+    "rc_engine_stretch_frames": (C.c_int, [_eng, C.c_void_p, _sz, C.c_uint32, _fp, _sz, C.POINTER(_sz)]),
     "rc_host_alloc": (C.c_int, [_sz, C.POINTER(C.c_void_p)]),
     "rc_host_free": (C.c_int, [C.c_void_p]),
     "rc_engine_stretch_device": (C.c_int, [_eng, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz,

@@ -130,6 +130,135 @@ struct ByteReader {
 uint32_t le32(const unsigned char *p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
 uint16_t le16(const unsigned char *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
 
+// the chunks in front of the samples: leaves `f` at the first byte of the data chunk (have_data; data_len as declared)
+struct WavHeader {
+    uint16_t fmt_tag = 0, channels = 0, bits = 0;
+    uint32_t rate = 0, data_len = 0;
+    bool have_fmt = false, have_data = false;
+};
+WavHeader read_wav_header(FILE *f) {
+    ByteReader r{f};
+    unsigned char hdr[12];
+    if (!r.read(hdr, 12) || memcmp(hdr, "RIFF", 4) || memcmp(hdr + 8, "WAVE", 4))
+        throw std::runtime_error("not a RIFF/WAVE stream");
+    WavHeader h;
+    for (;;) {
+        unsigned char ch[8];
+        if (!r.read(ch, 8)) break;
+        const uint32_t len = le32(ch + 4);
+        if (!memcmp(ch, "fmt ", 4)) {
+            if (len < 16 || len > 65536) throw std::runtime_error("bad fmt chunk");  // (a hostile length is not an allocation)
+            std::vector<unsigned char> b(len);
+            if (!r.read(b.data(), len)) throw std::runtime_error("bad fmt chunk");
+            h.fmt_tag = le16(&b[0]);
+            h.channels = le16(&b[2]);
+            h.rate = le32(&b[4]);
+            h.bits = le16(&b[14]);
+            if (h.fmt_tag == 0xFFFE && len >= 26) h.fmt_tag = le16(&b[24]);  // extensible: subformat
+            h.have_fmt = true;
+            if (len & 1) r.skip(1);
+        } else if (!memcmp(ch, "data", 4)) {
+            if (!h.have_fmt) throw std::runtime_error("data chunk before fmt chunk");
+            h.have_data = true;
+            h.data_len = len;
+            break;
+        } else {
+            if (!r.skip(len + (len & 1))) break;
+        }
+    }
+    if (!h.have_fmt || h.channels == 0) throw std::runtime_error("no fmt chunk");
+    if (h.bits / 8 == 0) throw std::runtime_error("unsupported bits per sample");
+    return h;
+}
+void check_wav_format(const WavHeader &h) {
+    const bool is_float = h.fmt_tag == 3, is_int = h.fmt_tag == 1;
+    if (!((is_float && h.bits == 32) || (is_int && (h.bits == 8 || h.bits == 16 || h.bits == 24 || h.bits == 32))))
+        throw std::runtime_error("Cannot read unsupported .wav format");  // audio_files.rs:184-186
+}
+
+// --frames-on-gpu: page-locked memory from the engine library and rc_engine_stretch_frames, looked up when the flag asks
+// for them (as the user-device-kernel entry points below: without the flag the CLI runs over a library that lacks them)
+struct FramesApi {
+    decltype(&rc_engine_stretch_frames) stretch = nullptr;
+    decltype(&rc_host_alloc) alloc = nullptr;
+    decltype(&rc_host_free) free = nullptr;
+};
+static const FramesApi &frames_api() {
+    static const FramesApi api = [] {
+        FramesApi a;
+        a.stretch = (decltype(a.stretch))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames");
+        a.alloc = (decltype(a.alloc))dlsym(RTLD_DEFAULT, "rc_host_alloc");
+        a.free = (decltype(a.free))dlsym(RTLD_DEFAULT, "rc_host_free");
+        if (!a.stretch || !a.alloc || !a.free) throw std::runtime_error("--frames-on-gpu: the engine library has no rc_engine_stretch_frames");
+        return a;
+    }();
+    return api;
+}
+struct PinnedBytes {
+    unsigned char *p = nullptr;
+    size_t n = 0;
+    PinnedBytes() = default;
+    explicit PinnedBytes(size_t bytes) : n(bytes) {
+        void *v = nullptr;
+        if (frames_api().alloc(std::max<size_t>(bytes, 1), &v) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+        p = (unsigned char *)v;
+    }
+    PinnedBytes(const PinnedBytes &) = delete;
+    PinnedBytes &operator=(const PinnedBytes &) = delete;
+    PinnedBytes(PinnedBytes &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+    PinnedBytes &operator=(PinnedBytes &&o) noexcept {
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+        return *this;
+    }
+    ~PinnedBytes() {
+        if (p) (void)frames_api().free(p);
+    }
+};
+// The data chunk as it is in the file, in page-locked memory: no sample is looked at on the host. `frames` whole frames
+// of `spec.channels` samples in `format` (RC_PCM_*) from data.p on.
+struct RawAudio {
+    AudioSpec spec;
+    uint32_t format = 0, sample_bytes = 0;
+    PinnedBytes data;
+    size_t frames = 0;
+};
+RawAudio read_wav_raw(FILE *f) {
+    const WavHeader h = read_wav_header(f);
+    check_wav_format(h);
+    RawAudio a;
+    a.spec.channels = h.channels;
+    a.spec.sample_rate = h.rate;
+    a.sample_bytes = h.bits / 8u;
+    a.format = h.fmt_tag == 3 ? RC_PCM_F32 : h.bits == 8 ? RC_PCM_U8 : h.bits == 16 ? RC_PCM_I16 : h.bits == 24 ? RC_PCM_I24 : RC_PCM_I32;
+    size_t got = 0;
+    if (h.have_data) {
+        const bool to_eof = h.data_len == 0xFFFFFFFFu || h.data_len == 0;
+        struct stat st {};
+        const long pos = ftell(f);
+        if (pos >= 0 && fstat(fileno(f), &st) == 0 && S_ISREG(st.st_mode)) {
+            // a file: the bytes it has, in one read (a declared length beyond the end costs nothing)
+            const size_t left = (size_t)st.st_size > (size_t)pos ? (size_t)st.st_size - (size_t)pos : 0;
+            a.data = PinnedBytes(to_eof ? left : std::min<size_t>(left, h.data_len));
+            got = fread(a.data.p, 1, a.data.n, f);
+        } else {  // a pipe: its length is known at its end
+            std::vector<unsigned char> raw, buf(1 << 20);
+            size_t left = to_eof ? SIZE_MAX : (size_t)h.data_len, k;
+            while (left && (k = fread(buf.data(), 1, std::min(left, buf.size()), f)) > 0) {
+                raw.insert(raw.end(), buf.begin(), buf.begin() + k);
+                left -= k;
+            }
+            a.data = PinnedBytes(raw.size());
+            if (!raw.empty()) memcpy(a.data.p, raw.data(), raw.size());
+            got = raw.size();
+        }
+    } else {
+        a.data = PinnedBytes(0);
+    }
+    a.frames = got / a.sample_bytes / h.channels;  // whole frames only, as read_wav
+    return a;
+}
+
 Audio read_wav(FILE *f) {
     ByteReader r{f};
     unsigned char hdr[12];
@@ -830,12 +959,16 @@ struct Opt {  // src/main.rs:27-122
     uint64_t seed = 0;  // not in the reference: thread_rng there
     int device = 0;
     std::vector<int32_t> devices;  // not in the reference: --devices a,b,... shards one job over several GPUs (rc_multi_*)
+    bool frames_on_gpu = false;    // not in the reference: the file's frames are unpacked and the output interleaved on the GPU
 };
 
 void usage() {
     fprintf(stderr,
             "rocoder (gfx950 engine)\nA live-codeable phase vocoder.\n\nUSAGE:\n    rocoder [FLAGS] [OPTIONS]\n\n"
-            "FLAGS:\n        --rotate-channels    Rotate the input audio channels\n    -h, --help\n\nOPTIONS:\n"
+            "FLAGS:\n        --rotate-channels    Rotate the input audio channels\n"
+            "        --frames-on-gpu      Decode the input's PCM frames and interleave the output on the GPU (one engine call;\n"
+            "                             not with --freq-kernel, --device-kernel-src, --devices, --rotate-channels)\n"
+            "    -h, --help\n\nOPTIONS:\n"
             "    -a, --amplitude <amplitude>        Output amplitude [default: 1]\n"
             "    -b, --buffer <buffer-dur>          The maximum amount of audio to process ahead of time [default: 1]\n"
             "    -d, --duration <duration>          Duration to use from input audio (hh:mm:ss.ss)\n"
@@ -897,6 +1030,7 @@ int run(int argc, char **argv) {
         else if (a == "-a" || a == "--amplitude") o.amplitude = strtof(need(i).c_str(), nullptr);
         else if (a == "-i" || a == "--input") o.input = need(i);
         else if (a == "--rotate-channels") o.rotate_channels = true;
+        else if (a == "--frames-on-gpu") o.frames_on_gpu = true;
         else if (a == "--freq-kernel") o.freq_kernel = need(i);
         else if (a == "--device-kernel") o.device_kernel = need(i);
         else if (a == "--device-kernel-src") o.device_kernel_src = need(i);
@@ -937,6 +1071,16 @@ int run(int argc, char **argv) {
     if (o.device_kernel_src && (o.freq_kernel || o.device_kernel))
         throw std::runtime_error("--device-kernel-src cannot be combined with --freq-kernel or --device-kernel");
     if (!o.dk_params.empty() && !o.device_kernel_src) throw std::runtime_error("--dk-params needs --device-kernel-src");
+    if (o.frames_on_gpu) {
+        // one engine call computes the whole job: nothing polls a watched kernel between windows, and the frame block is
+        // neither sharded nor reordered
+        const char *with = o.freq_kernel ? "--freq-kernel" : o.device_kernel_src ? "--device-kernel-src" : !o.devices.empty() ? "--devices"
+                           : o.rotate_channels ? "--rotate-channels" : nullptr;
+        if (with) {
+            fprintf(stderr, "error: --frames-on-gpu cannot be combined with %s\n", with);
+            return 2;
+        }
+    }
 
     // ROCODER_CLI_TIMING=1: wall time of each phase on stderr (dev aid)
     const bool timing = g_timing = getenv("ROCODER_CLI_TIMING") != nullptr;
@@ -950,12 +1094,28 @@ int run(int argc, char **argv) {
     // load_audio (src/main.rs:162-188)
     FILE *f = *o.input == "-" ? stdin : fopen(o.input->c_str(), "rb");
     if (!f) throw std::runtime_error("cannot open " + *o.input);
-    Audio audio = read_wav(f);
+    Audio audio;
+    RawAudio raw;
+    size_t raw_first = 0, raw_count = 0;  // --frames-on-gpu: -s / -d as a frame offset and count into raw.data
+    if (o.frames_on_gpu) {
+        raw = read_wav_raw(f);
+        raw_count = raw.frames;
+        if (o.start_ms || o.duration_ms) {  // Audio::clip_in_place
+            if (o.start_ms) raw_first = (size_t)((double)*o.start_ms / 1000.0 * (double)raw.spec.sample_rate);
+            size_t endp = raw.frames;
+            if (o.duration_ms) endp = raw_first + (size_t)((double)*o.duration_ms / 1000.0 * (double)raw.spec.sample_rate);
+            if (raw_first > raw.frames || endp > raw.frames || raw_first > endp)
+                throw std::runtime_error("clip range out of bounds (the reference panics on the slice)");
+            raw_count = endp - raw_first;
+        }
+    } else {
+        audio = read_wav(f);
+    }
     if (f != stdin) fclose(f);
-    if (o.start_ms || o.duration_ms) audio.clip_in_place(o.start_ms, o.duration_ms);
+    if (!o.frames_on_gpu && (o.start_ms || o.duration_ms)) audio.clip_in_place(o.start_ms, o.duration_ms);
     if (o.rotate_channels) audio.rotate_channels();
-    const size_t total_samples_len = audio.data.empty() ? 0 : audio.data[0].size();
-    const AudioSpec spec = audio.spec;
+    const size_t total_samples_len = o.frames_on_gpu ? raw_count : audio.data.empty() ? 0 : audio.data[0].size();
+    const AudioSpec spec = o.frames_on_gpu ? raw.spec : audio.spec;
     lap("read input");
 
     KernelStack kernels;
@@ -1004,6 +1164,37 @@ int run(int argc, char **argv) {
         } else {
             throw std::runtime_error("bad --device-kernel " + *o.device_kernel);
         }
+    }
+    if (o.frames_on_gpu) {
+        // the file's frames as they are -> rc_engine_stretch_frames -> the output file's frames: no sample is touched
+        // on the host. The same samples, so the same file, as the Stretcher / StretcherProcessor loop below writes.
+        Engine eng;
+        if (rc_engine_create(&cfg, &eng.h) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+        lap("engine create");
+        const size_t cap = rc_offline_output_len(&cfg, raw_count);
+        PinnedBytes out(cap * spec.channels * sizeof(float));
+        size_t n = 0;
+        const size_t frame_bytes = (size_t)spec.channels * raw.sample_bytes;
+        if (frames_api().stretch(eng.h, raw.data.p + raw_first * frame_bytes, raw_count, raw.format, (float *)out.p, cap, &n) != RC_OK)
+            throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+        lap("stretch");
+        // "<path>.part" first, as WavStreamWriter: a failed run leaves no output file
+        const std::string tmp = *o.output + ".part";
+        FILE *g = fopen(tmp.c_str(), "wb");
+        if (!g) throw std::runtime_error("cannot create " + tmp);
+        write_wav_header(g, spec, n);
+        const size_t total = n * spec.channels;
+        const bool ok = fwrite(out.p, sizeof(float), total, g) == total;
+        if (fclose(g) != 0 || !ok) {
+            (void)std::remove(tmp.c_str());
+            throw std::runtime_error("write failed (disk full?)");
+        }
+        if (std::rename(tmp.c_str(), o.output->c_str()) != 0) {
+            (void)std::remove(tmp.c_str());
+            throw std::runtime_error("cannot move " + tmp + " to " + *o.output);
+        }
+        lap("write output");
+        return 0;
     }
     if (!o.devices.empty()) {
         // several GPUs: the whole job at once through the multi-device entry (windows of a channel are independent

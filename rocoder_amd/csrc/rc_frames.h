@@ -1,0 +1,52 @@
+// Interleaved PCM frames <-> the engine's planar float rows (rc_engine_stretch_frames): parameter blocks and launcher
+// prototypes of rc_frames.hip. Kept apart from rc_kernels.h: these kernels move samples, they are no part of a hop
+// kernel family and of no family hash (tools/kernel_id.py).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace rc {
+
+// sample formats: the values of RC_PCM_* (include/rocoder_hip.h)
+enum : uint32_t { PCM_U8 = 1, PCM_I16 = 2, PCM_I24 = 3, PCM_I32 = 4, PCM_F32 = 5 };
+
+inline uint32_t pcm_bytes(uint32_t format) {
+    return format == PCM_U8 ? 1u : format == PCM_I16 ? 2u : format == PCM_I24 ? 3u : (format == PCM_I32 || format == PCM_F32) ? 4u : 0u;
+}
+
+// Tiles. Up to kNarrowChannels channels a tile is kNarrowFrames whole frames: one contiguous byte range of the frame
+// block. Above, a tile is kWideFrames frames x kWideChannels channels: one contiguous range per frame.
+constexpr uint32_t kFramesThreads = 256;
+constexpr uint32_t kNarrowChannels = 8, kNarrowFrames = 1024;
+constexpr uint32_t kWideChannels = 64, kWideFrames = 64;
+
+// frames [frame0, frame0 + n_frames) of a block of raw frames -> planar[c * stride + frame0 + i], every channel c.
+// Sample (f, c) of the block starts at byte `phase + (f * channels + c) * bytes` of `raw`; raw is 16-byte aligned
+// and holds raw_dwords (a multiple of 4) readable dwords, which cover every byte of the frames asked for. The kernel
+// reads whole 16-byte groups around its tile: bytes of those groups that belong to no frame of the tile are loaded
+// and never looked at.
+struct FramesUnpackParams {
+    const uint32_t *raw;
+    uint64_t raw_dwords;
+    uint32_t phase;  // 0 ... 3
+    uint32_t channels;
+    uint64_t frame0, n_frames;
+    float *planar;
+    uint64_t stride;  // floats between the rows of two channels
+};
+
+// planar[c * stride + i], i < n_frames, every channel c -> frames[(i) * channels + c]
+struct FramesPackParams {
+    const float *planar;
+    uint64_t stride;
+    float *frames;
+    uint64_t n_frames;
+    uint32_t channels;
+};
+
+// (both: nothing is launched for n_frames == 0; a job of more than 2^27 frames goes out as several launches)
+hipError_t launch_frames_unpack(uint32_t format, const FramesUnpackParams &p, hipStream_t s);
+hipError_t launch_frames_pack(const FramesPackParams &p, hipStream_t s);
+
+}  // namespace rc

@@ -367,6 +367,45 @@ class Engine:
         assert got.value == n_out
         return out[:, :n_out]
 
+    def stretch_frames(self, frames, fmt: Optional[str] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Interleaved PCM frames in, interleaved float32 frames out (rc_engine_stretch_frames): both format changes run
+        on the GPU, and the result is `stretch_host` of the decoded rows, transposed, bit for bit. `frames` is a
+        C-contiguous [n_frames, channels] array of uint8 / int16 / int32 / float32 (the format is the dtype's), or, with
+        an explicit `fmt` ("u8", "i16", "i24", "i32", "f32"), `bytes` or a uint8 array of whole little-endian frames at
+        any byte alignment - the only way to pass "i24". Returns [output_len, channels]; `out` (float32, C-contiguous,
+        [>= output_len, channels], e.g. from `pinned_empty`) is filled and its first output_len rows returned."""
+        by_dtype = {"uint8": "u8", "int16": "i16", "int32": "i32", "float32": "f32"}
+        if fmt is None:
+            a = np.asarray(frames)
+            if a.dtype.name not in by_dtype or a.ndim != 2:
+                raise ValueError("frames must be [n_frames, channels] uint8 / int16 / int32 / float32, or bytes with fmt=")
+            fmt = by_dtype[a.dtype.name]
+            if a.shape[1] != self.channels:
+                raise ValueError("channel count mismatch")
+        elif fmt not in _lib.PCM_FORMATS:
+            raise ValueError(f"fmt must be one of {sorted(_lib.PCM_FORMATS)}")
+        else:
+            a = np.frombuffer(frames, np.uint8) if isinstance(frames, (bytes, bytearray, memoryview)) else np.asarray(frames)
+        code = _lib.PCM_FORMATS[fmt]
+        if not a.flags.c_contiguous:
+            a = np.ascontiguousarray(a)
+        raw = a.reshape(-1).view(np.uint8)
+        frame_bytes = _lib.PCM_BYTES[code] * self.channels
+        if raw.size % frame_bytes:
+            raise ValueError(f"{raw.size} bytes are no whole number of {frame_bytes}-byte frames")
+        n = raw.size // frame_bytes
+        n_out = self.output_len(n)
+        if out is None:
+            out = np.empty((n_out, self.channels), np.float32)
+        elif (out.dtype != np.float32 or out.ndim != 2 or out.shape[1] != self.channels or out.shape[0] < n_out
+              or not out.flags.c_contiguous):
+            raise ValueError(f"out must be C-contiguous float32 [>= {n_out}, {self.channels}]")
+        got = C.c_size_t(0)
+        src = C.c_void_p(raw.ctypes.data if raw.size else out.ctypes.data)  # (no frames: any non-null pointer)
+        self._check(self._L.rc_engine_stretch_frames(self._h, src, n, code, _fp(out), out.shape[0], C.byref(got)))
+        assert got.value == n_out
+        return out[:n_out]
+
     def stretch_device_ptr(self, d_in: int, in_stride: int, in_len: int, d_out: int, out_stride: int,
                            out_cap: int, stream: int = 0) -> int:
         got = C.c_size_t(0)
