@@ -185,6 +185,27 @@ int rc_engine_stretch_host(rc_engine *e, const float *const *in, size_t in_len, 
 #define RC_PCM_F32 5
 int rc_engine_stretch_frames(rc_engine *e, const void *frames, size_t n_frames, uint32_t format,
                              float *out_frames, size_t out_cap_frames, size_t *out_frames_len);
+/* rc_engine_stretch_frames with the output as PCM frames of `out_format` (RC_PCM_*): the same job in the same pipeline,
+ * quantised and packed on the device, so that a 16-bit result crosses PCIe at half the bytes of its floats. out_frames
+ * receives rc_offline_output_len(cfg, n_frames) frames of `channels` little-endian samples and may sit at ANY byte
+ * alignment (a WAV data chunk inside a mapped file); no byte in front of or behind them is written. Float -> sample,
+ * bit for bit: t = x * (float)S, ONE IEEE f32 multiplication; r = rint(t), to nearest, ties to even, NaN -> 0; the
+ * integer written is r clamped to [LO, HI]:
+ *   RC_PCM_U8   S 127         [-128, 127]            written as the byte n + 128 (the inverse of hound's u8 -> i8)
+ *   RC_PCM_I16  S 32767       [-32768, 32767]        2 bytes
+ *   RC_PCM_I24  S 8388608     [-8388608, 8388607]    the low 3 bytes
+ *   RC_PCM_I32  S 2147483647  [-2^31, 2^31 - 1]      4 bytes ((float)S is 2^31; +1.0 gives 2^31 - 1, not INT_MIN)
+ *   RC_PCM_F32  the bits unchanged: the output of rc_engine_stretch_frames
+ * S is the divisor rc_engine_stretch_frames reads with, so decoding what this wrote and encoding it again gives the
+ * same bytes for u8 / i16 / i24. There is no dither and no noise shaping. *clipped (may be NULL) receives the number of
+ * output samples with !(|x| <= 1) - beyond full scale, or NaN - whatever out_format is, RC_PCM_F32 included: the
+ * stretch overshoots full scale regularly, and an integer format has to clip what a float file hides.
+ * RC_EINVAL: a null pointer (other than clipped), format or out_format outside 1 ... 5; RC_ECAPACITY: out_cap_frames too
+ * small. n_frames == 0 is valid and gives *clipped = 0. Pageable and page-locked memory both work on either side.
+ * Blocking: out_frames is complete on return. */
+int rc_engine_stretch_frames_pcm(rc_engine *e, const void *frames, size_t n_frames, uint32_t format,
+                                 void *out_frames, size_t out_cap_frames, uint32_t out_format,
+                                 size_t *out_frames_len, uint64_t *clipped);
 /* Page-locked host memory for the host-form calls (the `Vec<f32>` a Rust host would otherwise hand over, src/main.rs:
  * 148, src/audio.rs:152-172): rows allocated here cross PCIe without a staging copy. rc_host_free(NULL) is a no-op.
  * RC_ENODEVICE without a GPU, RC_ENOMEM when the pages cannot be locked. */

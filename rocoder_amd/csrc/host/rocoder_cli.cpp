@@ -180,6 +180,7 @@ void check_wav_format(const WavHeader &h) {
 // for them (as the user-device-kernel entry points below: without the flag the CLI runs over a library that lacks them)
 struct FramesApi {
     decltype(&rc_engine_stretch_frames) stretch = nullptr;
+    decltype(&rc_engine_stretch_frames_pcm) stretch_pcm = nullptr;  // (--output-format only: may be missing)
     decltype(&rc_host_alloc) alloc = nullptr;
     decltype(&rc_host_free) free = nullptr;
 };
@@ -187,6 +188,7 @@ static const FramesApi &frames_api() {
     static const FramesApi api = [] {
         FramesApi a;
         a.stretch = (decltype(a.stretch))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames");
+        a.stretch_pcm = (decltype(a.stretch_pcm))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames_pcm");
         a.alloc = (decltype(a.alloc))dlsym(RTLD_DEFAULT, "rc_host_alloc");
         a.free = (decltype(a.free))dlsym(RTLD_DEFAULT, "rc_host_free");
         if (!a.stretch || !a.alloc || !a.free) throw std::runtime_error("--frames-on-gpu: the engine library has no rc_engine_stretch_frames");
@@ -259,7 +261,7 @@ RawAudio read_wav_raw(FILE *f) {
     return a;
 }
 
-Audio read_wav(FILE *f) {
+Audio read_wav(FILE *f, uint32_t *format = nullptr) {
     ByteReader r{f};
     unsigned char hdr[12];
     if (!r.read(hdr, 12) || memcmp(hdr, "RIFF", 4) || memcmp(hdr + 8, "WAVE", 4))
@@ -315,6 +317,7 @@ Audio read_wav(FILE *f) {
     const bool is_float = fmt_tag == 3, is_int = fmt_tag == 1;
     if (!((is_float && bits == 32) || (is_int && (bits == 8 || bits == 16 || bits == 24 || bits == 32))))
         throw std::runtime_error("Cannot read unsupported .wav format");  // audio_files.rs:184-186
+    if (format) *format = is_float ? RC_PCM_F32 : bits == 8 ? RC_PCM_U8 : bits == 16 ? RC_PCM_I16 : bits == 24 ? RC_PCM_I24 : RC_PCM_I32;
     for (size_t i = 0; i < n; ++i) {
         const unsigned char *p = raw.data() + i * bps;
         float v;
@@ -336,45 +339,101 @@ Audio read_wav(FILE *f) {
     return a;
 }
 
-// 32-bit float WAV as hound writes it (audio_files.rs:68-81,203-226): WAVE_FORMAT_EXTENSIBLE header + interleaved frames
-void write_wav_header(FILE *f, const AudioSpec &spec, uint64_t frames) {
-    const uint32_t ch = spec.channels, rate = spec.sample_rate;
-    const uint64_t data_bytes = frames * ch * 4;
+// --output-format: float -> PCM sample, the definition of include/rocoder_hip.h (rc_engine_stretch_frames_pcm) and, bit
+// for bit, what the engine's pack kernel computes: t = x * S is one IEEE multiplication (nothing to fuse it with),
+// rint rounds to nearest even (the default rounding mode), NaN gives 0, the result is clamped. No dither.
+uint32_t pcm_sample_bytes(uint32_t fmt) { return fmt == RC_PCM_U8 ? 1u : fmt == RC_PCM_I16 ? 2u : fmt == RC_PCM_I24 ? 3u : 4u; }
+inline void pcm_encode(float x, uint32_t fmt, unsigned char *dst) {
+    if (fmt == RC_PCM_F32) {
+        memcpy(dst, &x, 4);
+        return;
+    }
+    const float S = fmt == RC_PCM_U8 ? 127.0f : fmt == RC_PCM_I16 ? 32767.0f : fmt == RC_PCM_I24 ? 8388608.0f : 2147483648.0f;
+    const double lo = fmt == RC_PCM_U8 ? -128.0 : fmt == RC_PCM_I16 ? -32768.0 : fmt == RC_PCM_I24 ? -8388608.0 : -2147483648.0;
+    const double hi = fmt == RC_PCM_U8 ? 127.0 : fmt == RC_PCM_I16 ? 32767.0 : fmt == RC_PCM_I24 ? 8388607.0 : 2147483647.0;
+    volatile float t = x * S;  // (volatile: rounded to f32 here, whatever the target's evaluation method)
+    double r = std::rint((double)t);  // (t is an f32: its nearest integer is the same in double)
+    if (std::isnan(r)) r = 0.0;
+    r = std::min(std::max(r, lo), hi);
+    const int32_t n = (int32_t)r;
+    const uint32_t u = fmt == RC_PCM_U8 ? (uint32_t)(n + 128) : (uint32_t)n;
+    for (uint32_t b = 0; b < pcm_sample_bytes(fmt); ++b) dst[b] = (unsigned char)(u >> (8 * b));
+}
+inline bool pcm_clipped(float x) { return !(std::fabs(x) <= 1.0f); }  // beyond full scale, or NaN
+
+// WAV as hound writes 32-bit float (audio_files.rs:68-81,203-226): WAVE_FORMAT_EXTENSIBLE header + interleaved frames.
+// The integer formats of --output-format get the same header with the PCM subformat and their own bits, block_align
+// and byte_rate; a data chunk of odd length is followed by a pad byte (write_wav_pad), counted in the RIFF size.
+void write_wav_header(FILE *f, const AudioSpec &spec, uint64_t frames, uint32_t fmt = RC_PCM_F32) {
+    const uint32_t ch = spec.channels, rate = spec.sample_rate, sb = pcm_sample_bytes(fmt);
+    const uint64_t data_bytes = frames * ch * sb;
     auto w32 = [&](uint32_t v) { fwrite(&v, 4, 1, f); };
     auto w16 = [&](uint16_t v) { fwrite(&v, 2, 1, f); };
     fwrite("RIFF", 1, 4, f);
-    w32((uint32_t)std::min<uint64_t>(0xFFFFFFFFu, 4 + 8 + 40 + 8 + data_bytes));
+    w32((uint32_t)std::min<uint64_t>(0xFFFFFFFFu, 4 + 8 + 40 + 8 + data_bytes + (data_bytes & 1)));
     fwrite("WAVE", 1, 4, f);
     fwrite("fmt ", 1, 4, f);
     w32(40);  // WAVE_FORMAT_EXTENSIBLE, as hound writes 32-bit float
     w16(0xFFFE);
     w16((uint16_t)ch);
     w32(rate);
-    w32(rate * ch * 4);
-    w16((uint16_t)(ch * 4));
-    w16(32);
+    w32(rate * ch * sb);
+    w16((uint16_t)(ch * sb));
+    w16((uint16_t)(8 * sb));
     w16(22);
-    w16(32);
+    w16((uint16_t)(8 * sb));
     w32(0);  // channel mask
-    const unsigned char guid_float[16] = {0x03, 0x00, 0x00, 0x00, 0x00, 0x00, 0x10, 0x00,
-                                          0x80, 0x00, 0x00, 0xaa, 0x00, 0x38, 0x9b, 0x71};
-    fwrite(guid_float, 1, 16, f);
+    const unsigned char guid[16] = {(unsigned char)(fmt == RC_PCM_F32 ? 0x03 : 0x01), 0x00, 0x00, 0x00, 0x00, 0x00, 0x10, 0x00,
+                                    0x80, 0x00, 0x00, 0xaa, 0x00, 0x38, 0x9b, 0x71};  // KSDATAFORMAT_SUBTYPE_IEEE_FLOAT / _PCM
+    fwrite(guid, 1, 16, f);
     fwrite("data", 1, 4, f);
     w32((uint32_t)std::min<uint64_t>(0xFFFFFFFFu, data_bytes));
 }
+bool write_wav_pad(FILE *f, const AudioSpec &spec, uint64_t frames, uint32_t fmt) {
+    return !((frames * spec.channels * pcm_sample_bytes(fmt)) & 1) || fputc(0, f) == 0;
+}
 
-void write_wav_f32(const std::string &path, const Audio &a) {
+// interleave and encode k frames from chans[c] + i0 into `row` (k * channels * bytes); returns the clipped samples
+uint64_t encode_frames(const float *const *chans, uint32_t ch, size_t i0, size_t k, uint32_t fmt, unsigned char *row) {
+    const uint32_t sb = pcm_sample_bytes(fmt);
+    uint64_t clipped = 0;
+    for (size_t i = 0; i < k; ++i)
+        for (uint32_t c = 0; c < ch; ++c) {
+            const float x = chans[c][i0 + i];
+            clipped += pcm_clipped(x);
+            pcm_encode(x, fmt, row + (i * ch + c) * sb);
+        }
+    return clipped;
+}
+
+// (*clipped, where given, receives the count of samples beyond full scale)
+void write_wav(const std::string &path, const Audio &a, uint32_t fmt = RC_PCM_F32, uint64_t *clipped = nullptr) {
     FILE *f = fopen(path.c_str(), "wb");
     if (!f) throw std::runtime_error("cannot create " + path);
     const uint32_t ch = a.spec.channels;
     const uint64_t frames = a.data.empty() ? 0 : a.data[0].size();
-    write_wav_header(f, a.spec, frames);
-    std::vector<float> row((size_t)ch * 4096);
-    for (uint64_t i0 = 0; i0 < frames; i0 += 4096) {
-        const uint64_t k = std::min<uint64_t>(4096, frames - i0);
-        for (uint64_t i = 0; i < k; ++i)
-            for (uint32_t c = 0; c < ch; ++c) row[i * ch + c] = a.data[c][i0 + i];  // interleave
-        fwrite(row.data(), 4, (size_t)(k * ch), f);
+    write_wav_header(f, a.spec, frames, fmt);
+    if (fmt == RC_PCM_F32 && !clipped) {
+        std::vector<float> row((size_t)ch * 4096);
+        for (uint64_t i0 = 0; i0 < frames; i0 += 4096) {
+            const uint64_t k = std::min<uint64_t>(4096, frames - i0);
+            for (uint64_t i = 0; i < k; ++i)
+                for (uint32_t c = 0; c < ch; ++c) row[i * ch + c] = a.data[c][i0 + i];  // interleave
+            fwrite(row.data(), 4, (size_t)(k * ch), f);
+        }
+    } else {
+        const uint32_t sb = pcm_sample_bytes(fmt);
+        std::vector<unsigned char> row((size_t)ch * 4096 * sb);
+        std::vector<const float *> chans;
+        for (auto &c : a.data) chans.push_back(c.data());
+        uint64_t n = 0;
+        for (uint64_t i0 = 0; i0 < frames; i0 += 4096) {
+            const uint64_t k = std::min<uint64_t>(4096, frames - i0);
+            n += encode_frames(chans.data(), ch, (size_t)i0, (size_t)k, fmt, row.data());
+            fwrite(row.data(), sb, (size_t)(k * ch), f);
+        }
+        (void)write_wav_pad(f, a.spec, frames, fmt);
+        if (clipped) *clipped = n;
     }
     fclose(f);
 }
@@ -382,20 +441,25 @@ void write_wav_f32(const std::string &path, const Audio &a) {
 // The same file written as the windows arrive (README.md:74 "stream output to disk instead of RAM", src/main.rs:197-203
 // collects the whole AudioBus first): the header goes out with the sizes still zero, every batch of windows that all
 // channels have delivered is interleaved and appended, and the two size fields are patched at the end - byte for
-// byte the file write_wav_f32 writes, with the resident set bounded by the queue depth instead of the output length.
+// byte the file write_wav writes, with the resident set bounded by the queue depth instead of the output length.
 struct WavStreamWriter {
     FILE *f = nullptr;
     AudioSpec spec;
     uint64_t frames = 0;
     std::vector<float> row;
+    std::vector<unsigned char> enc;
     std::string path, tmp;
+    uint32_t fmt = RC_PCM_F32;
+    bool count = false;    // --output-format given: samples are encoded through pcm_encode and the clipped ones counted
+    uint64_t clipped = 0;
     // The samples go to "<path>.part" and the file takes its name in finish(): a run that fails half way (a device
     // error, a full disk) leaves no output file with empty size fields behind (the reference writes nothing before the
     // whole output exists, src/main.rs:197-203)
-    WavStreamWriter(const std::string &path_, const AudioSpec &sp) : spec(sp), path(path_), tmp(path_ + ".part") {
+    WavStreamWriter(const std::string &path_, const AudioSpec &sp, uint32_t fmt_ = RC_PCM_F32, bool count_ = false)
+        : spec(sp), path(path_), tmp(path_ + ".part"), fmt(fmt_), count(count_) {
         f = fopen(tmp.c_str(), "wb");
         if (!f) throw std::runtime_error("cannot create " + tmp);
-        write_wav_header(f, spec, 0);
+        write_wav_header(f, spec, 0, fmt);
     }
     ~WavStreamWriter() {
         if (f) {  // not finished: drop the partial file
@@ -406,6 +470,17 @@ struct WavStreamWriter {
     // chans[c]: the next samples of channel c (equal lengths)
     void append(const std::vector<const float *> &chans, size_t n) {
         const uint32_t ch = spec.channels;
+        if (count) {
+            const uint32_t sb = pcm_sample_bytes(fmt);
+            enc.resize((size_t)ch * std::min<size_t>(n, 4096) * sb);
+            for (size_t i0 = 0; i0 < n; i0 += 4096) {
+                const size_t k = std::min<size_t>(4096, n - i0);
+                clipped += encode_frames(chans.data(), ch, i0, k, fmt, enc.data());
+                if (fwrite(enc.data(), sb, k * ch, f) != k * ch) throw std::runtime_error("write failed (disk full?)");
+            }
+            frames += n;
+            return;
+        }
         row.resize((size_t)ch * std::min<size_t>(n, 4096));
         for (size_t i0 = 0; i0 < n; i0 += 4096) {
             const size_t k = std::min<size_t>(4096, n - i0);
@@ -416,8 +491,9 @@ struct WavStreamWriter {
         frames += n;
     }
     void finish() {
+        if (!write_wav_pad(f, spec, frames, fmt)) throw std::runtime_error("write failed (disk full?)");
         if (fseek(f, 0, SEEK_SET) != 0) throw std::runtime_error("cannot seek in the output file");
-        write_wav_header(f, spec, frames);
+        write_wav_header(f, spec, frames, fmt);
         if (fclose(f) != 0) {
             f = nullptr;
             (void)std::remove(tmp.c_str());
@@ -940,6 +1016,10 @@ uint64_t drain_to_wav(WavStreamWriter &w, std::vector<std::shared_ptr<WindowQueu
     return w.frames;
 }
 
+uint32_t pcm_format_by_name(const std::string &s) {
+    return s == "u8" ? RC_PCM_U8 : s == "i16" ? RC_PCM_I16 : s == "i24" ? RC_PCM_I24 : s == "i32" ? RC_PCM_I32 : s == "f32" ? RC_PCM_F32 : 0u;
+}
+
 struct Opt {  // src/main.rs:27-122
     size_t window_len = 16384;
     uint64_t buffer_ms = 1000;
@@ -959,6 +1039,7 @@ struct Opt {  // src/main.rs:27-122
     uint64_t seed = 0;  // not in the reference: thread_rng there
     int device = 0;
     std::vector<int32_t> devices;  // not in the reference: --devices a,b,... shards one job over several GPUs (rc_multi_*)
+    std::optional<std::string> output_format;  // not in the reference (it writes f32): f32 | u8 | i16 | i24 | i32 | input
     bool frames_on_gpu = false;    // not in the reference: the file's frames are unpacked and the output interleaved on the GPU
 };
 
@@ -976,7 +1057,10 @@ void usage() {
             "    -f, --factor <factor>              Stretch factor [default: 1]\n"
             "        --freq-kernel <freq-kernel>    Path to a frequency kernel (.c/.cpp source or .so exporting `apply`)\n"
             "    -i, --input <input>                A .wav file; '-' for stdin\n"
-            "    -o, --output <output>              Output .wav file path. Uses 32-bit float.\n"
+            "    -o, --output <output>              Output .wav file path. 32-bit float unless --output-format says otherwise.\n"
+            "        --output-format <fmt>          Sample format of the output file: f32 | u8 | i16 | i24 | i32 | input (that of\n"
+            "                                       the input file) [default: f32]. Integers are rounded to nearest and clipped;\n"
+            "                                       the number of clipped samples is reported\n"
             "    -p, --pitch_multiple <n>           A non-zero integer pitch multiplier [default: 1]\n"
             "    -s, --start <start>                Start time in input audio (hh:mm:ss.ss)\n"
             "    -w, --window <window-len>          Processing window size [default: 16384]\n"
@@ -1012,6 +1096,44 @@ int run(int argc, char **argv) {
             if (parse_duration_ms(v, &ms)) printf("%llu\n", (unsigned long long)ms);
             else printf("error\n");
             return 0;
+        } else if (a == "--encode-pcm") {  // test hook: raw f32 samples -> the bytes --output-format <fmt> writes for them
+            const std::string name = need(i), in = need(i), outp = need(i);
+            const uint32_t fmt = pcm_format_by_name(name);
+            if (!fmt) throw std::runtime_error("bad format " + name);
+            FILE *f = fopen(in.c_str(), "rb");
+            if (!f) throw std::runtime_error("cannot open " + in);
+            std::vector<float> x;
+            float v;
+            while (fread(&v, 4, 1, f) == 1) x.push_back(v);
+            fclose(f);
+            std::vector<unsigned char> y(x.size() * pcm_sample_bytes(fmt) + 1);
+            const float *rows[1] = {x.data()};
+            const uint64_t clipped = encode_frames(rows, 1, 0, x.size(), fmt, y.data());
+            FILE *g = fopen(outp.c_str(), "wb");
+            if (!g) throw std::runtime_error("cannot create " + outp);
+            fwrite(y.data(), 1, y.size() - 1, g);
+            fclose(g);
+            printf("%zu %llu\n", x.size(), (unsigned long long)clipped);
+            return 0;
+        } else if (a == "--encode-wav") {  // test hook: raw f32 planar [channels][frames] -> the WAV --output-format <fmt> writes
+            const std::string name = need(i), chs = need(i), rate = need(i), in = need(i), outp = need(i);
+            const uint32_t fmt = pcm_format_by_name(name);
+            Audio au;
+            au.spec.channels = (uint16_t)atoi(chs.c_str());
+            au.spec.sample_rate = (uint32_t)strtoul(rate.c_str(), nullptr, 10);
+            if (!fmt || !au.spec.channels) throw std::runtime_error("bad --encode-wav arguments");
+            FILE *f = fopen(in.c_str(), "rb");
+            if (!f) throw std::runtime_error("cannot open " + in);
+            std::vector<float> x;
+            float v;
+            while (fread(&v, 4, 1, f) == 1) x.push_back(v);
+            fclose(f);
+            const size_t frames = x.size() / au.spec.channels;
+            for (uint32_t c = 0; c < au.spec.channels; ++c) au.data.emplace_back(x.begin() + c * frames, x.begin() + (c + 1) * frames);
+            uint64_t clipped = 0;
+            write_wav(outp, au, fmt, &clipped);
+            printf("%zu %llu\n", frames, (unsigned long long)clipped);
+            return 0;
         } else if (a == "--decode-wav") {  // test hook: WAV -> raw f32 planar [channels][frames]
             const std::string in = need(i), outp = need(i);
             FILE *f = in == "-" ? stdin : fopen(in.c_str(), "rb");
@@ -1031,6 +1153,11 @@ int run(int argc, char **argv) {
         else if (a == "-i" || a == "--input") o.input = need(i);
         else if (a == "--rotate-channels") o.rotate_channels = true;
         else if (a == "--frames-on-gpu") o.frames_on_gpu = true;
+        else if (a == "--output-format") {
+            o.output_format = need(i);
+            if (!pcm_format_by_name(*o.output_format) && *o.output_format != "input")
+                throw std::runtime_error("--output-format takes f32, u8, i16, i24, i32 or input, not " + *o.output_format);
+        }
         else if (a == "--freq-kernel") o.freq_kernel = need(i);
         else if (a == "--device-kernel") o.device_kernel = need(i);
         else if (a == "--device-kernel-src") o.device_kernel_src = need(i);
@@ -1096,6 +1223,7 @@ int run(int argc, char **argv) {
     if (!f) throw std::runtime_error("cannot open " + *o.input);
     Audio audio;
     RawAudio raw;
+    uint32_t in_format = RC_PCM_F32;
     size_t raw_first = 0, raw_count = 0;  // --frames-on-gpu: -s / -d as a frame offset and count into raw.data
     if (o.frames_on_gpu) {
         raw = read_wav_raw(f);
@@ -1109,9 +1237,16 @@ int run(int argc, char **argv) {
             raw_count = endp - raw_first;
         }
     } else {
-        audio = read_wav(f);
+        audio = read_wav(f, &in_format);
     }
     if (f != stdin) fclose(f);
+    // --output-format: without the flag the file is the f32 file of old and nothing is counted or reported
+    const bool out_fmt_given = o.output_format.has_value();
+    const uint32_t out_fmt = !out_fmt_given ? (uint32_t)RC_PCM_F32 : *o.output_format == "input" ? (o.frames_on_gpu ? raw.format : in_format)
+                                                                                           : pcm_format_by_name(*o.output_format);
+    auto report_clipped = [&](uint64_t clipped, uint64_t samples) {
+        if (out_fmt_given && clipped) fprintf(stderr, "%llu of %llu samples clipped\n", (unsigned long long)clipped, (unsigned long long)samples);
+    };
     if (!o.frames_on_gpu && (o.start_ms || o.duration_ms)) audio.clip_in_place(o.start_ms, o.duration_ms);
     if (o.rotate_channels) audio.rotate_channels();
     const size_t total_samples_len = o.frames_on_gpu ? raw_count : audio.data.empty() ? 0 : audio.data[0].size();
@@ -1172,19 +1307,25 @@ int run(int argc, char **argv) {
         if (rc_engine_create(&cfg, &eng.h) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
         lap("engine create");
         const size_t cap = rc_offline_output_len(&cfg, raw_count);
-        PinnedBytes out(cap * spec.channels * sizeof(float));
+        const uint32_t out_sb = pcm_sample_bytes(out_fmt);
+        PinnedBytes out(cap * spec.channels * out_sb);
         size_t n = 0;
+        uint64_t clipped = 0;
         const size_t frame_bytes = (size_t)spec.channels * raw.sample_bytes;
-        if (frames_api().stretch(eng.h, raw.data.p + raw_first * frame_bytes, raw_count, raw.format, (float *)out.p, cap, &n) != RC_OK)
+        if (out_fmt_given) {  // quantised, packed and counted on the device
+            if (!frames_api().stretch_pcm) throw std::runtime_error("--output-format: the engine library has no rc_engine_stretch_frames_pcm");
+            if (frames_api().stretch_pcm(eng.h, raw.data.p + raw_first * frame_bytes, raw_count, raw.format, out.p, cap, out_fmt, &n, &clipped) != RC_OK)
+                throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+        } else if (frames_api().stretch(eng.h, raw.data.p + raw_first * frame_bytes, raw_count, raw.format, (float *)out.p, cap, &n) != RC_OK)
             throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
         lap("stretch");
         // "<path>.part" first, as WavStreamWriter: a failed run leaves no output file
         const std::string tmp = *o.output + ".part";
         FILE *g = fopen(tmp.c_str(), "wb");
         if (!g) throw std::runtime_error("cannot create " + tmp);
-        write_wav_header(g, spec, n);
+        write_wav_header(g, spec, n, out_fmt);
         const size_t total = n * spec.channels;
-        const bool ok = fwrite(out.p, sizeof(float), total, g) == total;
+        const bool ok = fwrite(out.p, out_sb, total, g) == total && write_wav_pad(g, spec, n, out_fmt);
         if (fclose(g) != 0 || !ok) {
             (void)std::remove(tmp.c_str());
             throw std::runtime_error("write failed (disk full?)");
@@ -1194,6 +1335,7 @@ int run(int argc, char **argv) {
             throw std::runtime_error("cannot move " + tmp + " to " + *o.output);
         }
         lap("write output");
+        report_clipped(clipped, total);
         return 0;
     }
     if (!o.devices.empty()) {
@@ -1229,8 +1371,10 @@ int run(int argc, char **argv) {
         if (rc != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
         for (auto &c : out.data) c.resize(n);
         lap("stretch");
-        write_wav_f32(*o.output, out);
+        uint64_t clipped = 0;
+        write_wav(*o.output, out, out_fmt, out_fmt_given ? &clipped : nullptr);
         lap("write output");
+        report_clipped(clipped, (uint64_t)n * spec.channels);
         return 0;
     }
     auto eng = std::make_shared<Engine>();
@@ -1267,17 +1411,20 @@ int run(int argc, char **argv) {
         proc.join();
         if (!proc.error.empty()) throw std::runtime_error(proc.error);
         lap("stretch");
-        write_wav_f32(*o.output, out);
+        uint64_t clipped = 0;
+        write_wav(*o.output, out, out_fmt, out_fmt_given ? &clipped : nullptr);
         lap("write output");
+        report_clipped(clipped, (out.data.empty() ? 0 : (uint64_t)out.data[0].size()) * spec.channels);
         return 0;
     }
-    WavStreamWriter wav(*o.output, spec);
+    WavStreamWriter wav(*o.output, spec, out_fmt, out_fmt_given);
     drain_to_wav(wav, bus);
     for (auto &q : bus) q->abandon();  // (only matters after a `stuck` exit: the processor must not block on a full queue)
     proc.join();
     if (!proc.error.empty()) throw std::runtime_error(proc.error);
     wav.finish();
     lap("stretch+write");
+    report_clipped(wav.clipped, wav.frames * spec.channels);
     return 0;
 }
 

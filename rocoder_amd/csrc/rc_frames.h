@@ -45,8 +45,33 @@ struct FramesPackParams {
     uint32_t channels;
 };
 
-// (both: nothing is launched for n_frames == 0; a job of more than 2^27 frames goes out as several launches)
+// planar[c * stride + i], i < n_frames, every channel c -> sample (i, c) of a frame-major block of PCM samples of `format`,
+// little endian, which starts at byte target + phase (target: 4-byte aligned; the block may start and end anywhere in a
+// dword). Quantisation, bit for bit what include/rocoder_hip.h states (rc_engine_stretch_frames_pcm):
+//   t = x * (float)S, ONE IEEE multiplication; r = rint(t), ties to even, NaN -> 0; n = r clamped to [LO, HI]
+//   U8   S 127         [-128, 127]          the byte n + 128
+//   I16  S 32767       [-32768, 32767]      2 bytes
+//   I24  S 8388608     [-8388608, 8388607]  the low 3 bytes
+//   I32  S 2147483647  [-2^31, 2^31 - 1]    4 bytes ((float)S is 2^31: clamped in float to +-2^31, then saturated)
+//   F32  the bits as they are
+// S is the reader's divisor, so decode(encode(.)) is the identity on what the reader gives for u8 / i16 / i24. No
+// dither and no noise shaping: out of scope. *clipped (device memory) grows by the number of samples with
+// !(|x| <= 1) - beyond full scale or NaN, whatever the format - by one atomic per workgroup that saw any.
+// The launch writes the n_frames * channels * bytes bytes of its frames and no other byte, each once and without
+// reading the target: a launch for the frames in front or behind may run, or be downloaded, at the same time.
+struct FramesPackPcmParams {
+    const float *planar;
+    uint64_t stride;
+    unsigned char *target;
+    uint32_t phase;  // 0 ... 3
+    uint32_t channels;
+    uint64_t n_frames;
+    uint64_t *clipped;
+};
+
+// (all: nothing is launched for n_frames == 0; a job of more than 2^27 frames goes out as several launches)
 hipError_t launch_frames_unpack(uint32_t format, const FramesUnpackParams &p, hipStream_t s);
 hipError_t launch_frames_pack(const FramesPackParams &p, hipStream_t s);
+hipError_t launch_frames_pack_pcm(uint32_t format, const FramesPackPcmParams &p, hipStream_t s);
 
 }  // namespace rc

@@ -135,7 +135,204 @@ __global__ __launch_bounds__(kFramesThreads) void frames_pack_wide_kernel(Frames
         for (uint32_t r = wave; r < tf; r += kWaves) p.frames[(f0 + r) * C + c0 + lane] = lds[r * kPitch + lane];
 }
 
+// ---- planar float rows -> integer (or float) PCM frames at any byte address (rc_engine_stretch_frames_pcm) ----------
+// The mirror image of the unpack kernels. Samples are quantised on their way into LDS, one per dword in frame order;
+// the target is then written as whole dwords assembled from them. With 1-, 2- and 3-byte samples and a byte phase the
+// byte ranges of neighbouring tiles (and of neighbouring launches, whose downloads are in flight) meet inside a dword.
+// No dword is read back and none is written twice: a dword belongs to the tile that holds its LAST byte, and that tile
+// also quantises the up to three samples in front of its own range that the dword starts with. Only the first and the
+// last dword of a launch can be partial; they are written byte by byte, the bytes of the launch's frames and no other.
+
+// the definition in rc_frames.h / include/rocoder_hip.h: t = x * S (one IEEE multiplication), rint, NaN -> 0, clamp
+template <uint32_t FMT>
+__device__ __forceinline__ uint32_t pcm_encode(float x) {
+    if (FMT == PCM_F32) return __float_as_uint(x);
+    constexpr float S = FMT == PCM_U8 ? 127.0f : FMT == PCM_I16 ? 32767.0f : FMT == PCM_I24 ? 8388608.0f : 2147483648.0f;
+    constexpr float LO = FMT == PCM_U8 ? -128.0f : FMT == PCM_I16 ? -32768.0f : FMT == PCM_I24 ? -8388608.0f : -2147483648.0f;
+    constexpr float HI = FMT == PCM_U8 ? 127.0f : FMT == PCM_I16 ? 32767.0f : FMT == PCM_I24 ? 8388607.0f : 2147483648.0f;
+    float r = rintf(__fmul_rn(x, S));
+    if (r != r) r = 0.0f;
+    r = fminf(fmaxf(r, LO), HI);
+    // (I32: 2^31 - 1 is no float; what the clamp leaves at 2^31 saturates)
+    const int32_t n = (FMT == PCM_I32 && r >= 2147483648.0f) ? 2147483647 : (int32_t)r;
+    return FMT == PCM_U8 ? (uint32_t)(n + 128) : (uint32_t)n;
+}
+
+__device__ __forceinline__ uint32_t pcm_is_clipped(float x) { return !(fabsf(x) <= 1.0f) ? 1u : 0u; }
+
+// `q` holds one encoded sample per dword. The byte `rel` bytes into the stream of their low B bytes each ...
+template <uint32_t B>
+__device__ __forceinline__ uint32_t stream_byte(const uint32_t *q, uint32_t rel) {
+    const uint32_t s = rel / B, k = rel - s * B;
+    return (q[s] >> (8u * k)) & 0xffu;
+}
+// ... and the four bytes from there on (every sample they belong to is in q)
+template <uint32_t B>
+__device__ __forceinline__ uint32_t stream_dword(const uint32_t *q, uint32_t rel) {
+    if (B == 4) {
+        const uint32_t s = rel >> 2, sh = (rel & 3u) * 8u, lo = q[s];
+        return sh ? (lo >> sh) | (q[s + 1] << (32u - sh)) : lo;
+    }
+    uint32_t s = rel / B, k = rel - s * B;
+    uint32_t v = q[s] >> (8u * k), w = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+        w |= (v & 0xffu) << (8u * j);
+        v >>= 8;
+        if (j < 3 && ++k == B) {
+            k = 0;
+            v = q[++s];
+        }
+    }
+    return w;
+}
+
+// bytes [lo, hi) of one dword, from stream byte `rel` of q on
+template <uint32_t B>
+__device__ __forceinline__ void store_bytes(const uint32_t *q, uint32_t rel, uintptr_t lo, uintptr_t hi) {
+    for (uintptr_t a = lo; a < hi; ++a) *(unsigned char *)a = (unsigned char)stream_byte<B>(q, rel + (uint32_t)(a - lo));
+}
+
+// per-lane counts -> one atomic of the workgroup (none where nothing clipped). Holds a barrier: every lane calls it.
+__device__ __forceinline__ void add_clipped(uint32_t n, uint32_t *block_sum, uint64_t *clipped) {
+    for (uint32_t off = 32; off; off >>= 1) n += __shfl_down(n, off);
+    if ((threadIdx.x & 63u) == 0 && n) atomicAdd(block_sum, n);
+    __syncthreads();
+    if (threadIdx.x == 0 && *block_sum) atomicAdd((unsigned long long *)clipped, (unsigned long long)*block_sum);
+}
+
+// LDS: 1024 frames of 8 channels + the frames in front that the first dword starts with (at most 3 bytes: 3 + channels
+// samples at the most)
+constexpr uint32_t kPcmLdsDwords = kNarrowFrames * kNarrowChannels + 16;
+
+template <uint32_t FMT>
+__global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_kernel(FramesPackPcmParams p) {
+    constexpr uint32_t B = fmt_bytes<FMT>();
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kPcmLdsDwords];
+    __shared__ uint32_t clip_sum;
+    const uint32_t C = p.channels, tid = threadIdx.x;
+    const uint64_t f0 = (uint64_t)blockIdx.x * kNarrowFrames;
+    if (f0 >= p.n_frames) return;
+    if (tid == 0) clip_sum = 0;
+    __syncthreads();
+    const uint32_t tf = (uint32_t)(p.n_frames - f0 < kNarrowFrames ? p.n_frames - f0 : kNarrowFrames);
+    const uintptr_t T = (uintptr_t)p.target + p.phase, END = T + p.n_frames * C * B;  // the launch's bytes
+    const uintptr_t g0 = T + f0 * C * B, g1 = g0 + (uintptr_t)tf * C * B;              // the tile's
+    const uintptr_t a0 = g0 & ~(uintptr_t)3;                                            // its first dword
+    const uintptr_t first = a0 > T ? a0 : T;                                            // its first byte
+    // whole frames in front of the tile that byte `first` reaches into (0 for the first tile: first == T == g0)
+    const uint32_t lead = ((uint32_t)(g0 - first) + C * B - 1) / (C * B);
+    const uintptr_t P = g0 - (uintptr_t)lead * C * B;  // where lds[0] lies in the target
+    const uint32_t sf = lead + tf;
+    uint32_t nclip = 0;
+    for (uint32_t c = 0; c < C; ++c) {
+        const float *row = p.planar + (uint64_t)c * p.stride + (f0 - lead);
+        for (uint32_t fl = tid; fl < sf; fl += kFramesThreads) {
+            const float x = row[fl];
+            lds[fl * C + c] = pcm_encode<FMT>(x);
+            if (fl >= lead) nclip += pcm_is_clipped(x);  // (a frame in front is counted by its own tile)
+        }
+    }
+    add_clipped(nclip, &clip_sum, p.clipped);  // (its barrier stands between the LDS stores above and the loads below)
+    // the launch's partial first and last dword, byte by byte (one and the same dword in a launch of under 4 bytes)
+    const uintptr_t t0 = END & ~(uintptr_t)3;
+    if (tid == 0 && a0 < T) store_bytes<B>(lds, 0, T, a0 + 4 < END ? a0 + 4 : END);
+    if (tid == 64 && g1 == END && (END & 3u) && t0 >= T) store_bytes<B>(lds, (uint32_t)(t0 - P), t0, END);
+    // whole dwords [d0, d1): 16-byte groups from the first aligned address on, single dwords around them
+    const uintptr_t d0 = a0 < T ? a0 + 4 : a0, d1 = g1 & ~(uintptr_t)3;
+    const uint32_t nd = d1 > d0 ? (uint32_t)((d1 - d0) >> 2) : 0u;
+    const uint32_t pre_want = (uint32_t)((16u - (d0 & 15u)) & 15u) >> 2, pre = pre_want < nd ? pre_want : nd;
+    const uint32_t n4 = (nd - pre) >> 2;
+    const uint32_t rel0 = (uint32_t)(d0 - P);
+    uint4 *dst4 = (uint4 *)(d0 + 4u * pre);
+    for (uint32_t k = tid; k < n4; k += kFramesThreads) {
+        const uint32_t rel = rel0 + 4u * pre + 16u * k;
+        dst4[k] = make_uint4(stream_dword<B>(lds, rel), stream_dword<B>(lds, rel + 4), stream_dword<B>(lds, rel + 8),
+                             stream_dword<B>(lds, rel + 12));
+    }
+    uint32_t *dst = (uint32_t *)d0;
+    if (tid < pre) dst[tid] = stream_dword<B>(lds, rel0 + 4u * tid);
+    const uint32_t i = pre + 4u * n4 + tid;
+    if (i < nd) dst[i] = stream_dword<B>(lds, rel0 + 4u * i);
+}
+
+// a row of the wide tile: 3 samples in front of the row's segment + 64 + odd
+constexpr uint32_t kPcmWidePitch = 69;
+
+template <uint32_t FMT>
+__global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_wide_kernel(FramesPackPcmParams p) {
+    constexpr uint32_t B = fmt_bytes<FMT>();
+    __shared__ uint32_t lds[kWideFrames * kPcmWidePitch];
+    __shared__ uint32_t clip_sum;
+    const uint32_t C = p.channels, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t f0 = (uint64_t)blockIdx.x * kWideFrames;
+    const uint32_t c0 = blockIdx.y * kWideChannels;
+    if (f0 >= p.n_frames || c0 >= C) return;
+    if (tid == 0) clip_sum = 0;
+    __syncthreads();
+    const uint32_t tf = (uint32_t)(p.n_frames - f0 < kWideFrames ? p.n_frames - f0 : kWideFrames);
+    const uint32_t tc = C - c0 < kWideChannels ? C - c0 : kWideChannels;
+    const uintptr_t T = (uintptr_t)p.target + p.phase, END = T + p.n_frames * C * B;
+    uint32_t nclip = 0;
+    if (lane < tf)
+        for (uint32_t c = wave; c < tc; c += kWaves) {
+            const float x = p.planar[(uint64_t)(c0 + c) * p.stride + f0 + lane];
+            lds[lane * kPcmWidePitch + 3 + c] = pcm_encode<FMT>(x);
+            nclip += pcm_is_clipped(x);
+        }
+    // the samples in front of a row's segment that its first dword starts with: sample e back ends at g0 - (e - 1) B
+    for (uint32_t i = tid; i < tf * 3u; i += kFramesThreads) {
+        const uint32_t r = i / 3u, e = i - r * 3u + 1u;
+        const uintptr_t g0 = T + ((f0 + r) * C + c0) * B, a0 = g0 & ~(uintptr_t)3, first = a0 > T ? a0 : T;
+        if (g0 - (e - 1u) * B > first) {  // (then it is a sample of the launch: its last byte is at or behind T)
+            const uint64_t f = c0 >= e ? f0 + r : f0 + r - 1;
+            const uint32_t c = c0 >= e ? c0 - e : C + c0 - e;
+            lds[r * kPcmWidePitch + 3 - e] = pcm_encode<FMT>(p.planar[(uint64_t)c * p.stride + f]);
+        }
+    }
+    add_clipped(nclip, &clip_sum, p.clipped);
+    for (uint32_t r = wave; r < tf; r += kWaves) {
+        const uint32_t *row = lds + r * kPcmWidePitch;
+        const uintptr_t g0 = T + ((f0 + r) * C + c0) * B, g1 = g0 + (uintptr_t)tc * B;
+        const uintptr_t P = g0 - 3u * B;  // where row[0] would lie in the target
+        const uintptr_t a0 = g0 & ~(uintptr_t)3, a1 = g1 == END ? (g1 + 3) & ~(uintptr_t)3 : g1 & ~(uintptr_t)3;
+        for (uintptr_t a = a0 + 4u * lane; a < a1; a += 256) {  // at most 65 dwords
+            if (a >= T && a + 4 <= END) {
+                *(uint32_t *)a = stream_dword<B>(row, (uint32_t)(a - P));
+            } else {
+                const uintptr_t lo = a > T ? a : T, hi = a + 4 < END ? a + 4 : END;
+                store_bytes<B>(row, (uint32_t)(lo - P), lo, hi);
+            }
+        }
+    }
+}
+
 constexpr uint64_t kMaxFramesPerLaunch = (uint64_t)1 << 27;  // (a grid dimension times the block stays far below 2^32)
+
+template <uint32_t FMT>
+hipError_t pack_pcm_fmt(const FramesPackPcmParams &p, hipStream_t s) {
+    constexpr uint32_t B = fmt_bytes<FMT>();
+    const bool narrow = p.channels <= kNarrowChannels;
+    const uint32_t per = narrow ? kNarrowFrames : kWideFrames;
+    for (uint64_t done = 0; done < p.n_frames; done += kMaxFramesPerLaunch) {
+        FramesPackPcmParams q = p;
+        const uint64_t off = p.phase + done * p.channels * B;
+        q.planar = p.planar + done;
+        q.target = p.target + (off & ~(uint64_t)3);
+        q.phase = (uint32_t)(off & 3u);
+        q.n_frames = p.n_frames - done < kMaxFramesPerLaunch ? p.n_frames - done : kMaxFramesPerLaunch;
+        const uint32_t tiles = (uint32_t)((q.n_frames + per - 1) / per);
+        if (narrow) {
+            frames_pack_pcm_kernel<FMT><<<dim3(tiles), dim3(kFramesThreads), 0, s>>>(q);
+        } else {
+            const uint32_t ct = (p.channels + kWideChannels - 1) / kWideChannels;
+            frames_pack_pcm_wide_kernel<FMT><<<dim3(tiles, ct), dim3(kFramesThreads), 0, s>>>(q);
+        }
+        const hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
 
 template <uint32_t FMT>
 hipError_t unpack_fmt(const FramesUnpackParams &p, hipStream_t s) {
@@ -195,6 +392,19 @@ hipError_t launch_frames_pack(const FramesPackParams &p, hipStream_t s) {
         if (err != hipSuccess) return err;
     }
     return hipSuccess;
+}
+
+hipError_t launch_frames_pack_pcm(uint32_t format, const FramesPackPcmParams &p, hipStream_t s) {
+    if (!pcm_bytes(format)) return hipErrorInvalidValue;
+    if (p.n_frames == 0) return hipSuccess;
+    if (p.channels == 0 || p.channels > 65535u || p.phase > 3u || ((uintptr_t)p.target & 3u) || !p.clipped) return hipErrorInvalidValue;
+    switch (format) {
+    case PCM_U8: return pack_pcm_fmt<PCM_U8>(p, s);
+    case PCM_I16: return pack_pcm_fmt<PCM_I16>(p, s);
+    case PCM_I24: return pack_pcm_fmt<PCM_I24>(p, s);
+    case PCM_I32: return pack_pcm_fmt<PCM_I32>(p, s);
+    default: return pack_pcm_fmt<PCM_F32>(p, s);
+    }
 }
 
 }  // namespace rc

@@ -367,13 +367,23 @@ class Engine:
         assert got.value == n_out
         return out[:, :n_out]
 
-    def stretch_frames(self, frames, fmt: Optional[str] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+    last_clipped: Optional[int] = None  # stretch_frames(out_fmt=...): output samples beyond full scale (or NaN) of the last call
+
+    def stretch_frames(self, frames, fmt: Optional[str] = None, out: Optional[np.ndarray] = None,
+                       out_fmt: Optional[str] = None) -> np.ndarray:
         """Interleaved PCM frames in, interleaved float32 frames out (rc_engine_stretch_frames): both format changes run
         on the GPU, and the result is `stretch_host` of the decoded rows, transposed, bit for bit. `frames` is a
         C-contiguous [n_frames, channels] array of uint8 / int16 / int32 / float32 (the format is the dtype's), or, with
         an explicit `fmt` ("u8", "i16", "i24", "i32", "f32"), `bytes` or a uint8 array of whole little-endian frames at
         any byte alignment - the only way to pass "i24". Returns [output_len, channels]; `out` (float32, C-contiguous,
-        [>= output_len, channels], e.g. from `pinned_empty`) is filled and its first output_len rows returned."""
+        [>= output_len, channels], e.g. from `pinned_empty`) is filled and its first output_len rows returned.
+
+        With `out_fmt` ("u8", "i16", "i24", "i32", "f32") the result is quantised and packed on the GPU as well
+        (rc_engine_stretch_frames_pcm; x * S rounded to nearest even and clamped, S = 127 / 32767 / 8388608 / 2147483647):
+        "i16" returns '<i2', "i32" '<i4', "u8" uint8 and "f32" float32, each [output_len, channels]; "i24" returns uint8
+        [output_len, channels, 3], the samples' little-endian bytes. `out` is then any C-contiguous writable array of at
+        least that many bytes, at any byte alignment; it is filled from its first byte, nothing else of it is written,
+        and the result is a view of it. `last_clipped` holds the number of output samples beyond full scale."""
         by_dtype = {"uint8": "u8", "int16": "i16", "int32": "i32", "float32": "f32"}
         if fmt is None:
             a = np.asarray(frames)
@@ -395,6 +405,26 @@ class Engine:
             raise ValueError(f"{raw.size} bytes are no whole number of {frame_bytes}-byte frames")
         n = raw.size // frame_bytes
         n_out = self.output_len(n)
+        if out_fmt is not None:
+            if out_fmt not in _lib.PCM_FORMATS:
+                raise ValueError(f"out_fmt must be one of {sorted(_lib.PCM_FORMATS)}")
+            ocode = _lib.PCM_FORMATS[out_fmt]
+            dtype, tail = {"u8": (np.uint8, ()), "i16": ("<i2", ()), "i24": (np.uint8, (3,)), "i32": ("<i4", ()),
+                           "f32": ("<f4", ())}[out_fmt]
+            need = n_out * self.channels * _lib.PCM_BYTES[ocode]
+            if out is None:
+                out = np.empty(max(need, 1), np.uint8)
+            elif not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.flags.writeable and out.nbytes >= need):
+                raise ValueError(f"out must be a C-contiguous writable array of at least {need} bytes")
+            dst = out.reshape(-1).view(np.uint8)
+            got, clipped = C.c_size_t(0), C.c_uint64(0)
+            src = C.c_void_p(raw.ctypes.data if raw.size else dst.ctypes.data)  # (no frames: any non-null pointer)
+            self._check(self._L.rc_engine_stretch_frames_pcm(
+                self._h, src, n, code, C.c_void_p(dst.ctypes.data), dst.size // (self.channels * _lib.PCM_BYTES[ocode]),
+                ocode, C.byref(got), C.byref(clipped)))
+            assert got.value == n_out
+            self.last_clipped = int(clipped.value)
+            return dst[:need].view(dtype).reshape((n_out, self.channels) + tail)
         if out is None:
             out = np.empty((n_out, self.channels), np.float32)
         elif (out.dtype != np.float32 or out.ndim != 2 or out.shape[1] != self.channels or out.shape[0] < n_out

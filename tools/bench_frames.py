@@ -78,7 +78,7 @@ class PackParams(C.Structure):  # rc::FramesPackParams
 def launcher(Lib, name):
     """The C++ launchers are no part of the C-ABI: found by their mangled names in the library's dynamic symbols."""
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    sym = [ln.split()[-1] for ln in out.splitlines() if name in ln]
+    sym = [ln.split()[-1] for ln in out.splitlines() if f"{len(name)}{name}E" in ln]  # (the whole name: not launch_frames_pack_pcm)
     assert len(sym) == 1, (name, sym)
     fn = getattr(Lib, sym[0])
     fn.restype = C.c_int
