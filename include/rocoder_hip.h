@@ -206,6 +206,31 @@ int rc_engine_stretch_frames(rc_engine *e, const void *frames, size_t n_frames, 
 int rc_engine_stretch_frames_pcm(rc_engine *e, const void *frames, size_t n_frames, uint32_t format,
                                  void *out_frames, size_t out_cap_frames, uint32_t out_format,
                                  size_t *out_frames_len, uint64_t *clipped);
+/* rc_engine_stretch_frames_pcm with the result peak-normalised on the device: the peak of the whole job is measured there,
+ * and every sample is multiplied by one gain in front of the quantiser, so that an integer file needs no second run at
+ * a guessed amplitude. The same job otherwise: the input formats, the output formats (RC_PCM_F32 included), any byte
+ * alignment on both sides, no byte in front of or behind the result written, pageable or page-locked memory, blocking.
+ * The definition, bit for bit:
+ *   y      the f32 result of rc_engine_stretch_frames on the same input: all channels, all frames.
+ *   peak   the largest |y| among the samples with |y| < inf; NaN and +-inf are skipped. 0.0f when there is no such
+ *          sample or all are zero.
+ *   gain   target_peak / peak, ONE IEEE f32 division, when peak > 0 and that quotient is finite; otherwise 1.0f.
+ *   z      y * gain, ONE IEEE f32 multiplication, not contracted with the quantiser's multiplication by S; denormals
+ *          are kept.
+ *   bytes  exactly what rc_engine_stretch_frames_pcm writes for a planar result z: the quantiser stated above, and the
+ *          bits of z themselves for RC_PCM_F32.
+ *   *clipped  the number of samples with !(|z| <= 1), counted after the gain.
+ * peak * gain can round one ulp above target_peak: with target_peak == 1 the peak sample itself may therefore be
+ * counted in *clipped. The integer formats write it as full scale either way.
+ * peak, gain and clipped may each be NULL. RC_EINVAL: what rc_engine_stretch_frames_pcm rejects, and a target_peak that
+ * is not finite or not > 0; RC_ECAPACITY: out_cap_frames too small. n_frames == 0 is valid and gives peak 0, gain 1,
+ * clipped 0. On any error nothing behind the out-pointers is written.
+ * The job runs in two phases over the engine's pipeline - compute and measure, then pack and download - and the gain is
+ * formed on the device between them: there is no host round trip, and nothing is held that the other two frame
+ * entries do not hold already. */
+int rc_engine_stretch_frames_norm(rc_engine *e, const void *frames, size_t n_frames, uint32_t format, void *out_frames,
+                                  size_t out_cap_frames, uint32_t out_format, float target_peak,
+                                  size_t *out_frames_len, float *peak, float *gain, uint64_t *clipped);
 /* Page-locked host memory for the host-form calls (the `Vec<f32>` a Rust host would otherwise hand over, src/main.rs:
  * 148, src/audio.rs:152-172): rows allocated here cross PCIe without a staging copy. rc_host_free(NULL) is a no-op.
  * RC_ENODEVICE without a GPU, RC_ENOMEM when the pages cannot be locked. */

@@ -84,6 +84,10 @@ extern "C" {
     pub fn rc_engine_stretch_frames_pcm(e: *mut RcEngine, frames: *const c_void, n_frames: usize, format: u32,
                                         out_frames: *mut c_void, out_cap_frames: usize, out_format: u32,
                                         out_frames_len: *mut usize, clipped: *mut u64) -> c_int;
+    pub fn rc_engine_stretch_frames_norm(e: *mut RcEngine, frames: *const c_void, n_frames: usize, format: u32,
+                                         out_frames: *mut c_void, out_cap_frames: usize, out_format: u32,
+                                         target_peak: f32, out_frames_len: *mut usize, peak: *mut f32,
+                                         gain: *mut f32, clipped: *mut u64) -> c_int;
     pub fn rc_host_alloc(bytes: usize, out: *mut *mut c_void) -> c_int;   // page-locked rows: no staging copy
     pub fn rc_host_free(p: *mut c_void) -> c_int;
     pub fn rc_engine_stretch_device(e: *mut RcEngine, d_in: *const f32, in_stride: usize, in_len: usize,

@@ -107,6 +107,9 @@ SYMBOLS = {
     "rc_engine_stretch_frames": (C.c_int, [_eng, C.c_void_p, _sz, C.c_uint32, _fp, _sz, C.POINTER(_sz)]),
     "rc_engine_stretch_frames_pcm": (C.c_int, [_eng, C.c_void_p, _sz, C.c_uint32, C.c_void_p, _sz, C.c_uint32,
                                                C.POINTER(_sz), C.POINTER(C.c_uint64)]),
+    "rc_engine_stretch_frames_norm": (C.c_int, [_eng, C.c_void_p, _sz, C.c_uint32, C.c_void_p, _sz, C.c_uint32, C.c_float,
+                                                C.POINTER(_sz), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                C.POINTER(C.c_uint64)]),
     "rc_host_alloc": (C.c_int, [_sz, C.POINTER(C.c_void_p)]),
     "rc_host_free": (C.c_int, [C.c_void_p]),
     "rc_engine_stretch_device": (C.c_int, [_eng, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz,

@@ -181,6 +181,7 @@ void check_wav_format(const WavHeader &h) {
 struct FramesApi {
     decltype(&rc_engine_stretch_frames) stretch = nullptr;
     decltype(&rc_engine_stretch_frames_pcm) stretch_pcm = nullptr;  // (--output-format only: may be missing)
+    decltype(&rc_engine_stretch_frames_norm) stretch_norm = nullptr;  // (--normalize only: may be missing)
     decltype(&rc_host_alloc) alloc = nullptr;
     decltype(&rc_host_free) free = nullptr;
 };
@@ -189,6 +190,7 @@ static const FramesApi &frames_api() {
         FramesApi a;
         a.stretch = (decltype(a.stretch))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames");
         a.stretch_pcm = (decltype(a.stretch_pcm))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames_pcm");
+        a.stretch_norm = (decltype(a.stretch_norm))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames_norm");
         a.alloc = (decltype(a.alloc))dlsym(RTLD_DEFAULT, "rc_host_alloc");
         a.free = (decltype(a.free))dlsym(RTLD_DEFAULT, "rc_host_free");
         if (!a.stretch || !a.alloc || !a.free) throw std::runtime_error("--frames-on-gpu: the engine library has no rc_engine_stretch_frames");
@@ -1041,6 +1043,7 @@ struct Opt {  // src/main.rs:27-122
     std::vector<int32_t> devices;  // not in the reference: --devices a,b,... shards one job over several GPUs (rc_multi_*)
     std::optional<std::string> output_format;  // not in the reference (it writes f32): f32 | u8 | i16 | i24 | i32 | input
     bool frames_on_gpu = false;    // not in the reference: the file's frames are unpacked and the output interleaved on the GPU
+    std::optional<float> normalize;  // not in the reference: the output's peak is brought to this level on the GPU (--frames-on-gpu)
 };
 
 void usage() {
@@ -1061,6 +1064,9 @@ void usage() {
             "        --output-format <fmt>          Sample format of the output file: f32 | u8 | i16 | i24 | i32 | input (that of\n"
             "                                       the input file) [default: f32]. Integers are rounded to nearest and clipped;\n"
             "                                       the number of clipped samples is reported\n"
+            "        --normalize <peak>             With --frames-on-gpu: measure the peak of the whole output on the GPU and scale\n"
+            "                                       it to <peak> (1 = full scale) in front of the quantiser, any --output-format;\n"
+            "                                       peak and gain are reported\n"
             "    -p, --pitch_multiple <n>           A non-zero integer pitch multiplier [default: 1]\n"
             "    -s, --start <start>                Start time in input audio (hh:mm:ss.ss)\n"
             "    -w, --window <window-len>          Processing window size [default: 16384]\n"
@@ -1158,6 +1164,14 @@ int run(int argc, char **argv) {
             if (!pcm_format_by_name(*o.output_format) && *o.output_format != "input")
                 throw std::runtime_error("--output-format takes f32, u8, i16, i24, i32 or input, not " + *o.output_format);
         }
+        else if (a == "--normalize") {
+            const std::string v = need(i);
+            char *end = nullptr;
+            const float t = strtof(v.c_str(), &end);
+            if (v.empty() || *end || !(t > 0.0f) || !std::isfinite(t))
+                throw std::runtime_error("--normalize takes a finite peak level above 0, not " + v);
+            o.normalize = t;
+        }
         else if (a == "--freq-kernel") o.freq_kernel = need(i);
         else if (a == "--device-kernel") o.device_kernel = need(i);
         else if (a == "--device-kernel-src") o.device_kernel_src = need(i);
@@ -1198,6 +1212,9 @@ int run(int argc, char **argv) {
     if (o.device_kernel_src && (o.freq_kernel || o.device_kernel))
         throw std::runtime_error("--device-kernel-src cannot be combined with --freq-kernel or --device-kernel");
     if (!o.dk_params.empty() && !o.device_kernel_src) throw std::runtime_error("--dk-params needs --device-kernel-src");
+    // the peak of the whole output has to be known before its first sample is written: the streamed host writer never
+    // holds the whole output, the engine under --frames-on-gpu does
+    if (o.normalize && !o.frames_on_gpu) throw std::runtime_error("--normalize needs --frames-on-gpu");
     if (o.frames_on_gpu) {
         // one engine call computes the whole job: nothing polls a watched kernel between windows, and the frame block is
         // neither sharded nor reordered
@@ -1245,7 +1262,7 @@ int run(int argc, char **argv) {
     const uint32_t out_fmt = !out_fmt_given ? (uint32_t)RC_PCM_F32 : *o.output_format == "input" ? (o.frames_on_gpu ? raw.format : in_format)
                                                                                            : pcm_format_by_name(*o.output_format);
     auto report_clipped = [&](uint64_t clipped, uint64_t samples) {
-        if (out_fmt_given && clipped) fprintf(stderr, "%llu of %llu samples clipped\n", (unsigned long long)clipped, (unsigned long long)samples);
+        if ((out_fmt_given || o.normalize) && clipped) fprintf(stderr, "%llu of %llu samples clipped\n", (unsigned long long)clipped, (unsigned long long)samples);
     };
     if (!o.frames_on_gpu && (o.start_ms || o.duration_ms)) audio.clip_in_place(o.start_ms, o.duration_ms);
     if (o.rotate_channels) audio.rotate_channels();
@@ -1312,7 +1329,14 @@ int run(int argc, char **argv) {
         size_t n = 0;
         uint64_t clipped = 0;
         const size_t frame_bytes = (size_t)spec.channels * raw.sample_bytes;
-        if (out_fmt_given) {  // quantised, packed and counted on the device
+        if (o.normalize) {  // measured, scaled, quantised, packed and counted on the device
+            if (!frames_api().stretch_norm) throw std::runtime_error("--normalize: the engine library has no rc_engine_stretch_frames_norm");
+            float peak = 0.0f, gain = 1.0f;
+            if (frames_api().stretch_norm(eng.h, raw.data.p + raw_first * frame_bytes, raw_count, raw.format, out.p, cap, out_fmt, *o.normalize,
+                                          &n, &peak, &gain, &clipped) != RC_OK)
+                throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+            fprintf(stderr, "peak %.9g, gain %.9g\n", (double)peak, (double)gain);  // (nine digits: the f32 values exactly)
+        } else if (out_fmt_given) {  // quantised, packed and counted on the device
             if (!frames_api().stretch_pcm) throw std::runtime_error("--output-format: the engine library has no rc_engine_stretch_frames_pcm");
             if (frames_api().stretch_pcm(eng.h, raw.data.p + raw_first * frame_bytes, raw_count, raw.format, out.p, cap, out_fmt, &n, &clipped) != RC_OK)
                 throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());

@@ -69,9 +69,43 @@ struct FramesPackPcmParams {
     uint64_t *clipped;
 };
 
+// Peak normalisation (rc_engine_stretch_frames_norm): two device words of the engine, zeroed in front of a job.
+//   peak_bits  the bits of the largest |x| among the finite samples seen so far (for non-negative floats the unsigned
+//              order of the bits is the order of the values; NaN and +-inf are skipped: their bits sort above every
+//              finite value). 0 where nothing finite and non-zero was seen.
+//   gain       what the pack launches multiplied by, stored by the first of them for the host to read back
+struct FramesNormWords {
+    uint32_t peak_bits;
+    float gain;
+};
+
+// planar[c * stride + i], i < n_frames, every channel c: norm->peak_bits = max(norm->peak_bits, bits of |x|) over the
+// finite samples, by one atomicMax per workgroup that saw a non-zero one. A maximum does not depend on the order.
+struct FramesPeakParams {
+    const float *planar;
+    uint64_t stride;
+    uint64_t n_frames;
+    uint32_t channels;
+    FramesNormWords *norm;
+};
+
+// FramesPackPcmParams with a gain in front of the quantiser. Every lane forms the gain itself from the peak word:
+//   peak = the float of norm->peak_bits;  gain = target_peak / peak, ONE IEEE division, where peak > 0 and the quotient
+//   is finite, else 1;  z = x * gain, ONE IEEE multiplication (not contracted with the quantiser's x * S; denormals kept)
+// and z takes the place of x in the encoding and in the count of clipped samples. With store_gain set, one thread of
+// the first launch stores the gain to norm->gain.
+struct FramesPackPcmGainParams {
+    FramesPackPcmParams pack;
+    FramesNormWords *norm;
+    float target_peak;
+    uint32_t store_gain;
+};
+
 // (all: nothing is launched for n_frames == 0; a job of more than 2^27 frames goes out as several launches)
 hipError_t launch_frames_unpack(uint32_t format, const FramesUnpackParams &p, hipStream_t s);
 hipError_t launch_frames_pack(const FramesPackParams &p, hipStream_t s);
 hipError_t launch_frames_pack_pcm(uint32_t format, const FramesPackPcmParams &p, hipStream_t s);
+hipError_t launch_frames_peak(const FramesPeakParams &p, hipStream_t s);
+hipError_t launch_frames_pack_pcm_gain(uint32_t format, const FramesPackPcmGainParams &p, hipStream_t s);
 
 }  // namespace rc

@@ -201,18 +201,42 @@ __device__ __forceinline__ void add_clipped(uint32_t n, uint32_t *block_sum, uin
     if (threadIdx.x == 0 && *block_sum) atomicAdd((unsigned long long *)clipped, (unsigned long long)*block_sum);
 }
 
+// The pack kernels below are templates over their parameter block: FramesPackPcmParams (rc_engine_stretch_frames_pcm:
+// the samples as they are) or FramesPackPcmGainParams (rc_engine_stretch_frames_norm: every sample times a gain that
+// each lane forms from the peak word - one correctly rounded division, the definition in rc_frames.h). The first
+// instantiation is the kernel it was before the second existed: NoGain is the identity and holds nothing.
+struct NoGain {
+    __device__ __forceinline__ float operator()(float x) const { return x; }
+};
+struct Gain {
+    float g;
+    // (an intrinsic: never contracted with the quantiser's multiplication by S)
+    __device__ __forceinline__ float operator()(float x) const { return __fmul_rn(x, g); }
+};
+__host__ __device__ __forceinline__ const FramesPackPcmParams &pack_of(const FramesPackPcmParams &p) { return p; }
+__host__ __device__ __forceinline__ const FramesPackPcmParams &pack_of(const FramesPackPcmGainParams &p) { return p.pack; }
+__device__ __forceinline__ NoGain gain_of(const FramesPackPcmParams &) { return NoGain{}; }
+__device__ __forceinline__ Gain gain_of(const FramesPackPcmGainParams &p) {
+    const float peak = __uint_as_float(p.norm->peak_bits), q = __fdiv_rn(p.target_peak, peak);
+    const float g = (peak > 0.0f && q < __builtin_inff()) ? q : 1.0f;
+    if (p.store_gain && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.norm->gain = g;
+    return Gain{g};
+}
+
 // LDS: 1024 frames of 8 channels + the frames in front that the first dword starts with (at most 3 bytes: 3 + channels
 // samples at the most)
 constexpr uint32_t kPcmLdsDwords = kNarrowFrames * kNarrowChannels + 16;
 
-template <uint32_t FMT>
-__global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_kernel(FramesPackPcmParams p) {
+template <uint32_t FMT, class PP>
+__global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_kernel(PP pp) {
     constexpr uint32_t B = fmt_bytes<FMT>();
     __shared__ __attribute__((aligned(16))) uint32_t lds[kPcmLdsDwords];
     __shared__ uint32_t clip_sum;
+    const FramesPackPcmParams &p = pack_of(pp);
     const uint32_t C = p.channels, tid = threadIdx.x;
     const uint64_t f0 = (uint64_t)blockIdx.x * kNarrowFrames;
     if (f0 >= p.n_frames) return;
+    const auto gain = gain_of(pp);
     if (tid == 0) clip_sum = 0;
     __syncthreads();
     const uint32_t tf = (uint32_t)(p.n_frames - f0 < kNarrowFrames ? p.n_frames - f0 : kNarrowFrames);
@@ -228,7 +252,7 @@ __global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_kernel(FramesP
     for (uint32_t c = 0; c < C; ++c) {
         const float *row = p.planar + (uint64_t)c * p.stride + (f0 - lead);
         for (uint32_t fl = tid; fl < sf; fl += kFramesThreads) {
-            const float x = row[fl];
+            const float x = gain(row[fl]);
             lds[fl * C + c] = pcm_encode<FMT>(x);
             if (fl >= lead) nclip += pcm_is_clipped(x);  // (a frame in front is counted by its own tile)
         }
@@ -259,15 +283,17 @@ __global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_kernel(FramesP
 // a row of the wide tile: 3 samples in front of the row's segment + 64 + odd
 constexpr uint32_t kPcmWidePitch = 69;
 
-template <uint32_t FMT>
-__global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_wide_kernel(FramesPackPcmParams p) {
+template <uint32_t FMT, class PP>
+__global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_wide_kernel(PP pp) {
     constexpr uint32_t B = fmt_bytes<FMT>();
     __shared__ uint32_t lds[kWideFrames * kPcmWidePitch];
     __shared__ uint32_t clip_sum;
+    const FramesPackPcmParams &p = pack_of(pp);
     const uint32_t C = p.channels, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint64_t f0 = (uint64_t)blockIdx.x * kWideFrames;
     const uint32_t c0 = blockIdx.y * kWideChannels;
     if (f0 >= p.n_frames || c0 >= C) return;
+    const auto gain = gain_of(pp);
     if (tid == 0) clip_sum = 0;
     __syncthreads();
     const uint32_t tf = (uint32_t)(p.n_frames - f0 < kWideFrames ? p.n_frames - f0 : kWideFrames);
@@ -276,7 +302,7 @@ __global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_wide_kernel(Fr
     uint32_t nclip = 0;
     if (lane < tf)
         for (uint32_t c = wave; c < tc; c += kWaves) {
-            const float x = p.planar[(uint64_t)(c0 + c) * p.stride + f0 + lane];
+            const float x = gain(p.planar[(uint64_t)(c0 + c) * p.stride + f0 + lane]);
             lds[lane * kPcmWidePitch + 3 + c] = pcm_encode<FMT>(x);
             nclip += pcm_is_clipped(x);
         }
@@ -287,7 +313,7 @@ __global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_wide_kernel(Fr
         if (g0 - (e - 1u) * B > first) {  // (then it is a sample of the launch: its last byte is at or behind T)
             const uint64_t f = c0 >= e ? f0 + r : f0 + r - 1;
             const uint32_t c = c0 >= e ? c0 - e : C + c0 - e;
-            lds[r * kPcmWidePitch + 3 - e] = pcm_encode<FMT>(p.planar[(uint64_t)c * p.stride + f]);
+            lds[r * kPcmWidePitch + 3 - e] = pcm_encode<FMT>(gain(p.planar[(uint64_t)c * p.stride + f]));
         }
     }
     add_clipped(nclip, &clip_sum, p.clipped);
@@ -307,26 +333,73 @@ __global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_wide_kernel(Fr
     }
 }
 
+// ---- the peak of planar rows (rc_engine_stretch_frames_norm, phase 1) ---------------------------------------------------
+// A workgroup takes kPeakSegment samples of one row (blockIdx.y: the channel): 16-byte loads from the segment's first
+// aligned address on, single dwords at its ragged ends (rows start at any float: a chunk's range, a stride of any length).
+constexpr uint32_t kPeakSegment = 8192;
+
+// the bits of |x| for a finite x, 0 for NaN and +-inf (whose bits would sort above every finite value)
+__device__ __forceinline__ uint32_t peak_bits_of(float x) {
+    const uint32_t b = __float_as_uint(x) & 0x7fffffffu;
+    return b < 0x7f800000u ? b : 0u;
+}
+
+__global__ __launch_bounds__(kFramesThreads) void frames_peak_kernel(FramesPeakParams p) {
+    __shared__ uint32_t wave_max[kFramesThreads / 64];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t s0 = (uint64_t)blockIdx.x * kPeakSegment;
+    if (s0 >= p.n_frames) return;  // (the whole workgroup)
+    const uint32_t len = (uint32_t)(p.n_frames - s0 < kPeakSegment ? p.n_frames - s0 : kPeakSegment);
+    const float *q = p.planar + (uint64_t)blockIdx.y * p.stride + s0;
+    const uint32_t head_want = (uint32_t)((16u - ((uintptr_t)q & 15u)) & 15u) >> 2, head = head_want < len ? head_want : len;
+    const uint32_t n4 = (len - head) >> 2;
+    uint32_t m = 0;
+    if (tid < head) m = peak_bits_of(q[tid]);
+    const float4 *q4 = (const float4 *)(q + head);
+    for (uint32_t k = tid; k < n4; k += kFramesThreads) {
+        const float4 v = q4[k];
+        m = max(max(m, peak_bits_of(v.x)), max(peak_bits_of(v.y), max(peak_bits_of(v.z), peak_bits_of(v.w))));
+    }
+    const uint32_t t = head + 4u * n4 + tid;  // (at most 3 behind the groups)
+    if (t < len) m = max(m, peak_bits_of(q[t]));
+    for (uint32_t off = 32; off; off >>= 1) m = max(m, (uint32_t)__shfl_down(m, off));
+    if ((tid & 63u) == 0) wave_max[tid >> 6] = m;
+    __syncthreads();
+    if (tid == 0) {
+        for (uint32_t w = 1; w < kFramesThreads / 64; ++w) m = max(m, wave_max[w]);
+        if (m) atomicMax(&p.norm->peak_bits, m);
+    }
+}
+
 constexpr uint64_t kMaxFramesPerLaunch = (uint64_t)1 << 27;  // (a grid dimension times the block stays far below 2^32)
 
-template <uint32_t FMT>
-hipError_t pack_pcm_fmt(const FramesPackPcmParams &p, hipStream_t s) {
+// the launches after the first of a job of more than kMaxFramesPerLaunch frames: the gain is stored once
+inline FramesPackPcmParams &pack_of(FramesPackPcmParams &p) { return p; }
+inline FramesPackPcmParams &pack_of(FramesPackPcmGainParams &p) { return p.pack; }
+inline void next_launch(FramesPackPcmParams &) {}
+inline void next_launch(FramesPackPcmGainParams &p) { p.store_gain = 0; }
+
+template <uint32_t FMT, class PP>
+hipError_t pack_pcm_fmt(const PP &pp, hipStream_t s) {
     constexpr uint32_t B = fmt_bytes<FMT>();
+    const FramesPackPcmParams &p = pack_of(pp);
     const bool narrow = p.channels <= kNarrowChannels;
     const uint32_t per = narrow ? kNarrowFrames : kWideFrames;
+    PP qq = pp;
     for (uint64_t done = 0; done < p.n_frames; done += kMaxFramesPerLaunch) {
-        FramesPackPcmParams q = p;
+        FramesPackPcmParams &q = pack_of(qq);
         const uint64_t off = p.phase + done * p.channels * B;
         q.planar = p.planar + done;
         q.target = p.target + (off & ~(uint64_t)3);
         q.phase = (uint32_t)(off & 3u);
         q.n_frames = p.n_frames - done < kMaxFramesPerLaunch ? p.n_frames - done : kMaxFramesPerLaunch;
+        if (done) next_launch(qq);
         const uint32_t tiles = (uint32_t)((q.n_frames + per - 1) / per);
         if (narrow) {
-            frames_pack_pcm_kernel<FMT><<<dim3(tiles), dim3(kFramesThreads), 0, s>>>(q);
+            frames_pack_pcm_kernel<FMT, PP><<<dim3(tiles), dim3(kFramesThreads), 0, s>>>(qq);
         } else {
             const uint32_t ct = (p.channels + kWideChannels - 1) / kWideChannels;
-            frames_pack_pcm_wide_kernel<FMT><<<dim3(tiles, ct), dim3(kFramesThreads), 0, s>>>(q);
+            frames_pack_pcm_wide_kernel<FMT, PP><<<dim3(tiles, ct), dim3(kFramesThreads), 0, s>>>(qq);
         }
         const hipError_t err = hipGetLastError();
         if (err != hipSuccess) return err;
@@ -404,6 +477,37 @@ hipError_t launch_frames_pack_pcm(uint32_t format, const FramesPackPcmParams &p,
     case PCM_I24: return pack_pcm_fmt<PCM_I24>(p, s);
     case PCM_I32: return pack_pcm_fmt<PCM_I32>(p, s);
     default: return pack_pcm_fmt<PCM_F32>(p, s);
+    }
+}
+
+hipError_t launch_frames_peak(const FramesPeakParams &p, hipStream_t s) {
+    if (p.n_frames == 0) return hipSuccess;
+    if (p.channels == 0 || p.channels > 65535u || !p.norm) return hipErrorInvalidValue;
+    for (uint64_t done = 0; done < p.n_frames; done += kMaxFramesPerLaunch) {
+        FramesPeakParams q = p;
+        q.planar = p.planar + done;
+        q.n_frames = p.n_frames - done < kMaxFramesPerLaunch ? p.n_frames - done : kMaxFramesPerLaunch;
+        const uint32_t segs = (uint32_t)((q.n_frames + kPeakSegment - 1) / kPeakSegment);
+        frames_peak_kernel<<<dim3(segs, p.channels), dim3(kFramesThreads), 0, s>>>(q);
+        const hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_frames_pack_pcm_gain(uint32_t format, const FramesPackPcmGainParams &pp, hipStream_t s) {
+    const FramesPackPcmParams &p = pp.pack;
+    if (!pcm_bytes(format)) return hipErrorInvalidValue;
+    if (p.n_frames == 0) return hipSuccess;
+    if (p.channels == 0 || p.channels > 65535u || p.phase > 3u || ((uintptr_t)p.target & 3u) || !p.clipped || !pp.norm ||
+        !(pp.target_peak > 0.0f && pp.target_peak < __builtin_inff()))
+        return hipErrorInvalidValue;
+    switch (format) {
+    case PCM_U8: return pack_pcm_fmt<PCM_U8>(pp, s);
+    case PCM_I16: return pack_pcm_fmt<PCM_I16>(pp, s);
+    case PCM_I24: return pack_pcm_fmt<PCM_I24>(pp, s);
+    case PCM_I32: return pack_pcm_fmt<PCM_I32>(pp, s);
+    default: return pack_pcm_fmt<PCM_F32>(pp, s);
     }
 }
 

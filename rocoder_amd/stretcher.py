@@ -368,9 +368,11 @@ class Engine:
         return out[:, :n_out]
 
     last_clipped: Optional[int] = None  # stretch_frames(out_fmt=...): output samples beyond full scale (or NaN) of the last call
+    last_peak: Optional[float] = None   # stretch_frames(normalize=...): the largest finite |sample| before the gain ...
+    last_gain: Optional[float] = None   # ... and the gain it was multiplied by (both np.float32)
 
     def stretch_frames(self, frames, fmt: Optional[str] = None, out: Optional[np.ndarray] = None,
-                       out_fmt: Optional[str] = None) -> np.ndarray:
+                       out_fmt: Optional[str] = None, normalize: Optional[float] = None) -> np.ndarray:
         """Interleaved PCM frames in, interleaved float32 frames out (rc_engine_stretch_frames): both format changes run
         on the GPU, and the result is `stretch_host` of the decoded rows, transposed, bit for bit. `frames` is a
         C-contiguous [n_frames, channels] array of uint8 / int16 / int32 / float32 (the format is the dtype's), or, with
@@ -383,7 +385,19 @@ class Engine:
         "i16" returns '<i2', "i32" '<i4', "u8" uint8 and "f32" float32, each [output_len, channels]; "i24" returns uint8
         [output_len, channels, 3], the samples' little-endian bytes. `out` is then any C-contiguous writable array of at
         least that many bytes, at any byte alignment; it is filled from its first byte, nothing else of it is written,
-        and the result is a view of it. `last_clipped` holds the number of output samples beyond full scale."""
+        and the result is a view of it. `last_clipped` holds the number of output samples beyond full scale.
+
+        With `normalize=p` (a finite float above 0) the result is peak-normalised on the GPU in front of the quantiser
+        (rc_engine_stretch_frames_norm): peak = the largest finite |sample| of the whole job, gain = p / peak in one f32
+        division (1 where the peak is 0 or the quotient overflows), every sample times gain in one f32 multiplication.
+        `out_fmt=None` then means "f32". `last_peak`, `last_gain` and `last_clipped` (counted after the gain) are set."""
+        if normalize is not None:
+            with np.errstate(over="ignore"):
+                normalize = float(np.float32(normalize))  # (the C-ABI takes an f32)
+            if not (normalize > 0 and np.isfinite(normalize)):
+                raise ValueError("normalize must be a finite float32 above 0")
+            if out_fmt is None:
+                out_fmt = "f32"
         by_dtype = {"uint8": "u8", "int16": "i16", "int32": "i32", "float32": "f32"}
         if fmt is None:
             a = np.asarray(frames)
@@ -419,9 +433,16 @@ class Engine:
             dst = out.reshape(-1).view(np.uint8)
             got, clipped = C.c_size_t(0), C.c_uint64(0)
             src = C.c_void_p(raw.ctypes.data if raw.size else dst.ctypes.data)  # (no frames: any non-null pointer)
-            self._check(self._L.rc_engine_stretch_frames_pcm(
-                self._h, src, n, code, C.c_void_p(dst.ctypes.data), dst.size // (self.channels * _lib.PCM_BYTES[ocode]),
-                ocode, C.byref(got), C.byref(clipped)))
+            cap = dst.size // (self.channels * _lib.PCM_BYTES[ocode])
+            if normalize is not None:
+                peak, gain = C.c_float(0), C.c_float(0)
+                self._check(self._L.rc_engine_stretch_frames_norm(
+                    self._h, src, n, code, C.c_void_p(dst.ctypes.data), cap, ocode, C.c_float(normalize), C.byref(got),
+                    C.byref(peak), C.byref(gain), C.byref(clipped)))
+                self.last_peak, self.last_gain = np.float32(peak.value), np.float32(gain.value)
+            else:
+                self._check(self._L.rc_engine_stretch_frames_pcm(
+                    self._h, src, n, code, C.c_void_p(dst.ctypes.data), cap, ocode, C.byref(got), C.byref(clipped)))
             assert got.value == n_out
             self.last_clipped = int(clipped.value)
             return dst[:need].view(dtype).reshape((n_out, self.channels) + tail)
