@@ -231,6 +231,38 @@ int rc_engine_stretch_frames_pcm(rc_engine *e, const void *frames, size_t n_fram
 int rc_engine_stretch_frames_norm(rc_engine *e, const void *frames, size_t n_frames, uint32_t format, void *out_frames,
                                   size_t out_cap_frames, uint32_t out_format, float target_peak,
                                   size_t *out_frames_len, float *peak, float *gain, uint64_t *clipped);
+/* The reference's sqrt fade-in / fade-out (`-x/--fade`, src/main.rs:91-97,206) on the result of the four whole-job
+ * host-form entries above - rc_engine_stretch_host, rc_engine_stretch_frames, rc_engine_stretch_frames_pcm and
+ * rc_engine_stretch_frames_norm - applied on the device to the planar f32 result, in front of everything that reads it.
+ * It is Audio::fade_in_at_sample(0, in_len) followed by Audio::fade_out_at_sample(out_start, out_len) (src/audio.rs:
+ * 81-113) with math::sqrt_interp (src/math.rs:33-40), its offline form - not the mixer's keyframes (src/mixer.rs:179-190),
+ * whose amplitude overshoots 1 between the end of a fade-in and the next chunk edge. The fade is engine state, set
+ * once: (0, RC_FADE_NONE, 0) clears it, and that is the state after rc_engine_create. All three are counts of output
+ * frames; every channel gets the same envelope. The definition, bit for bit:
+ *   T      the job's output length in frames (rc_offline_output_len); y[c][t] what rc_engine_stretch_host gives with
+ *          no fade set.
+ *   sq(p, d), p < d, every step ONE correctly rounded IEEE f32 operation, the integers converted to f32 with round to
+ *          nearest even:   r = (float)p / (float)d;   b = r * 2.0f - 1.0f;
+ *            rising   up(p, d)   = sqrtf(0.5f * (1.0f + fmaxf( b, -1.0f)))
+ *            falling  down(p, d) = sqrtf(0.5f * (1.0f + fmaxf(-b, -1.0f)))
+ *          (sqrt_interp(0, 1, r) and sqrt_interp(1, 0, r) without their `start + |end - start| * factor`, which is
+ *          exact for 0 and 1)
+ *   y1     t < in_len: y * up(t, in_len), ONE multiplication; otherwise y.
+ *   z      out_start <= t < out_start + out_len: y1 * down(t - out_start, out_len), ONE multiplication;
+ *          t >= out_start + out_len: +0.0f, assigned as the reference assigns it - whatever y1 was, NaN and negative
+ *          values included; otherwise y1. Where the two ranges overlap a sample is multiplied twice, in this order.
+ * in_len == 0 is no fade-in; out_start == RC_FADE_NONE is no fade-out; out_len == 0 is a hard cut at out_start.
+ * z takes the place of y in everything downstream: the peak and the gain of rc_engine_stretch_frames_norm, the
+ * quantiser, the count of clipped samples, the f32 frames and rows.
+ * Here: RC_EINVAL where out_start + out_len wraps (RC_FADE_NONE with an out_len included). At a call of one of the four
+ * entries: RC_EINVAL, before any work and with nothing written, where in_len > T or out_start + out_len > T (the
+ * reference logs "out of bounds, ignoring" there, src/audio.rs:82-85; a C-ABI caller is better served by a status).
+ * A job of no frames with a fade inside T = 0 is valid.
+ * The fade does NOT apply to the device-form entries (rc_engine_stretch_device, rc_engine_stretch_device_range), to
+ * the streaming seam (rc_engine_next_window ...) or to rc_multi: they return what they return without it, fade set or
+ * not. Only the frames a fade changes are touched: fades of 1 s cost 2 s of samples, not the job. */
+#define RC_FADE_NONE UINT64_MAX
+int rc_engine_set_output_fade(rc_engine *e, uint64_t in_len, uint64_t out_start, uint64_t out_len);
 /* Page-locked host memory for the host-form calls (the `Vec<f32>` a Rust host would otherwise hand over, src/main.rs:
  * 148, src/audio.rs:152-172): rows allocated here cross PCIe without a staging copy. rc_host_free(NULL) is a no-op.
  * RC_ENODEVICE without a GPU, RC_ENOMEM when the pages cannot be locked. */

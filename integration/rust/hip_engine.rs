@@ -88,6 +88,7 @@ extern "C" {
                                          out_frames: *mut c_void, out_cap_frames: usize, out_format: u32,
                                          target_peak: f32, out_frames_len: *mut usize, peak: *mut f32,
                                          gain: *mut f32, clipped: *mut u64) -> c_int;
+    pub fn rc_engine_set_output_fade(e: *mut RcEngine, in_len: u64, out_start: u64, out_len: u64) -> c_int;  // RC_FADE_NONE = u64::MAX
     pub fn rc_host_alloc(bytes: usize, out: *mut *mut c_void) -> c_int;   // page-locked rows: no staging copy
     pub fn rc_host_free(p: *mut c_void) -> c_int;
     pub fn rc_engine_stretch_device(e: *mut RcEngine, d_in: *const f32, in_stride: usize, in_len: usize,

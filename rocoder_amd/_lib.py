@@ -52,6 +52,7 @@ class rc_config(C.Structure):
 RC_DK_NONE, RC_DK_GAIN, RC_DK_BAND, RC_DK_SHIFT = 0, 1, 2, 3
 # rc_engine_stretch_frames: sample formats of interleaved PCM frames, and the bytes one sample takes
 RC_PCM_U8, RC_PCM_I16, RC_PCM_I24, RC_PCM_I32, RC_PCM_F32 = 1, 2, 3, 4, 5
+RC_FADE_NONE = 2**64 - 1  # rc_engine_set_output_fade: no fade-out
 PCM_FORMATS = {"u8": RC_PCM_U8, "i16": RC_PCM_I16, "i24": RC_PCM_I24, "i32": RC_PCM_I32, "f32": RC_PCM_F32}
 PCM_BYTES = {RC_PCM_U8: 1, RC_PCM_I16: 2, RC_PCM_I24: 3, RC_PCM_I32: 4, RC_PCM_F32: 4}
 
@@ -110,6 +111,7 @@ SYMBOLS = {
     "rc_engine_stretch_frames_norm": (C.c_int, [_eng, C.c_void_p, _sz, C.c_uint32, C.c_void_p, _sz, C.c_uint32, C.c_float,
                                                 C.POINTER(_sz), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                                 C.POINTER(C.c_uint64)]),
+    "rc_engine_set_output_fade": (C.c_int, [_eng, C.c_uint64, C.c_uint64, C.c_uint64]),
     "rc_host_alloc": (C.c_int, [_sz, C.POINTER(C.c_void_p)]),
     "rc_host_free": (C.c_int, [C.c_void_p]),
     "rc_engine_stretch_device": (C.c_int, [_eng, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz,

@@ -182,6 +182,7 @@ struct FramesApi {
     decltype(&rc_engine_stretch_frames) stretch = nullptr;
     decltype(&rc_engine_stretch_frames_pcm) stretch_pcm = nullptr;  // (--output-format only: may be missing)
     decltype(&rc_engine_stretch_frames_norm) stretch_norm = nullptr;  // (--normalize only: may be missing)
+    decltype(&rc_engine_set_output_fade) set_fade = nullptr;  // (--fade-output only: may be missing)
     decltype(&rc_host_alloc) alloc = nullptr;
     decltype(&rc_host_free) free = nullptr;
 };
@@ -191,6 +192,7 @@ static const FramesApi &frames_api() {
         a.stretch = (decltype(a.stretch))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames");
         a.stretch_pcm = (decltype(a.stretch_pcm))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames_pcm");
         a.stretch_norm = (decltype(a.stretch_norm))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames_norm");
+        a.set_fade = (decltype(a.set_fade))dlsym(RTLD_DEFAULT, "rc_engine_set_output_fade");
         a.alloc = (decltype(a.alloc))dlsym(RTLD_DEFAULT, "rc_host_alloc");
         a.free = (decltype(a.free))dlsym(RTLD_DEFAULT, "rc_host_free");
         if (!a.stretch || !a.alloc || !a.free) throw std::runtime_error("--frames-on-gpu: the engine library has no rc_engine_stretch_frames");
@@ -1043,6 +1045,7 @@ struct Opt {  // src/main.rs:27-122
     std::vector<int32_t> devices;  // not in the reference: --devices a,b,... shards one job over several GPUs (rc_multi_*)
     std::optional<std::string> output_format;  // not in the reference (it writes f32): f32 | u8 | i16 | i24 | i32 | input
     bool frames_on_gpu = false;    // not in the reference: the file's frames are unpacked and the output interleaved on the GPU
+    bool fade_output = false;      // not in the reference (it fades playback only): -x is applied to the output file, on the GPU (--frames-on-gpu)
     std::optional<float> normalize;  // not in the reference: the output's peak is brought to this level on the GPU (--frames-on-gpu)
 };
 
@@ -1056,7 +1059,10 @@ void usage() {
             "    -a, --amplitude <amplitude>        Output amplitude [default: 1]\n"
             "    -b, --buffer <buffer-dur>          The maximum amount of audio to process ahead of time [default: 1]\n"
             "    -d, --duration <duration>          Duration to use from input audio (hh:mm:ss.ss)\n"
-            "    -x, --fade <fade>                  Fade (playback only; accepted and ignored with -o) [default: 1]\n"
+            "    -x, --fade <fade>                  Fade (playback only; ignored with -o unless --fade-output is given) [default: 1]\n"
+            "        --fade-output                  With --frames-on-gpu: fade the output file in and out over -x, as the\n"
+            "                                       reference fades its playback, on the GPU in front of --normalize and the\n"
+            "                                       quantiser; a fade longer than the output is left out with a warning\n"
             "    -f, --factor <factor>              Stretch factor [default: 1]\n"
             "        --freq-kernel <freq-kernel>    Path to a frequency kernel (.c/.cpp source or .so exporting `apply`)\n"
             "    -i, --input <input>                A .wav file; '-' for stdin\n"
@@ -1159,6 +1165,7 @@ int run(int argc, char **argv) {
         else if (a == "-i" || a == "--input") o.input = need(i);
         else if (a == "--rotate-channels") o.rotate_channels = true;
         else if (a == "--frames-on-gpu") o.frames_on_gpu = true;
+        else if (a == "--fade-output") o.fade_output = true;
         else if (a == "--output-format") {
             o.output_format = need(i);
             if (!pcm_format_by_name(*o.output_format) && *o.output_format != "input")
@@ -1215,6 +1222,8 @@ int run(int argc, char **argv) {
     // the peak of the whole output has to be known before its first sample is written: the streamed host writer never
     // holds the whole output, the engine under --frames-on-gpu does
     if (o.normalize && !o.frames_on_gpu) throw std::runtime_error("--normalize needs --frames-on-gpu");
+    // (the fade is applied by the engine's whole-job calls: the streamed host writer has no such step)
+    if (o.fade_output && !o.frames_on_gpu) throw std::runtime_error("--fade-output needs --frames-on-gpu");
     if (o.frames_on_gpu) {
         // one engine call computes the whole job: nothing polls a watched kernel between windows, and the frame block is
         // neither sharded nor reordered
@@ -1325,6 +1334,22 @@ int run(int argc, char **argv) {
         lap("engine create");
         const size_t cap = rc_offline_output_len(&cfg, raw_count);
         const uint32_t out_sb = pcm_sample_bytes(out_fmt);
+        if (o.fade_output) {
+            // Layer::fade_in_out (src/mixer.rs:179-190) in frames: the fade-in over the first F frames, the fade-out over
+            // the F frames in front of expected_total_samples (src/main.rs:154); Audio::fade_*_at_sample's bounds checks
+            // and warnings (src/audio.rs:82-85,101-104) decide here, so that the engine call cannot fail on them
+            if (!frames_api().set_fade) throw std::runtime_error("--fade-output: the engine library has no rc_engine_set_output_fade");
+            const size_t fade = (size_t)((float)((double)o.fade_ms / 1000.0) * (float)spec.sample_rate);
+            const size_t expected = (size_t)((float)raw_count * o.factor);
+            const bool in_fits = fade <= cap, out_fits = expected <= cap && expected >= fade;
+            if (!in_fits) fprintf(stderr, "Fade in parameters out of bounds, ignoring.\n");
+            if (!out_fits) fprintf(stderr, "Fade out parameters out of bounds, ignoring.\n");
+            if (frames_api().set_fade(eng.h, in_fits ? fade : 0, out_fits ? expected - fade : RC_FADE_NONE, out_fits ? fade : 0) != RC_OK)
+                throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+            if (in_fits && out_fits) fprintf(stderr, "fade in %zu frames, out from %zu over %zu\n", fade, expected - fade, fade);
+            else if (in_fits) fprintf(stderr, "fade in %zu frames\n", fade);
+            else if (out_fits) fprintf(stderr, "fade out from %zu over %zu\n", expected - fade, fade);
+        }
         PinnedBytes out(cap * spec.channels * out_sb);
         size_t n = 0;
         uint64_t clipped = 0;

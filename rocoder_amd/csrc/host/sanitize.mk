@@ -7,7 +7,7 @@
 ROOT := ../../..
 CXX  ?= g++
 COMMON := -g -O1 -std=c++17 -Wall -fno-omit-frame-pointer rocoder_cli.cpp -ldl -lpthread
-all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../bin/engine_tsan ../../bin/engine_dk_asan ../../bin/engine_xch_asan ../../bin/engine_frames_asan ../../bin/engine_frames_pcm_asan ../../bin/engine_frames_norm_asan
+all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../bin/engine_tsan ../../bin/engine_dk_asan ../../bin/engine_xch_asan ../../bin/engine_frames_asan ../../bin/engine_frames_pcm_asan ../../bin/engine_frames_norm_asan ../../bin/engine_frames_fade_asan
 ../../bin/rocoder_asan: rocoder_cli.cpp $(ROOT)/include/rocoder_hip.h ../../librocoder_hip.so
 	mkdir -p ../../bin
 	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(COMMON) -o $@ -L../.. -lrocoder_hip \
@@ -22,7 +22,7 @@ all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../b
 # kernels compute nothing - driven by tests/c/engine_host_driver.cpp:
 #   ../../bin/engine_asan : -fsanitize=address,undefined      ../../bin/engine_tsan : -fsanitize=thread
 ENGINE_SRC := ../rc_engine.cpp ../rc_rtc.cpp $(ROOT)/tests/c/hip_stub.cpp $(ROOT)/tests/c/hip_stub_long.cpp \
-    $(ROOT)/tests/c/hip_stub_frames.cpp $(ROOT)/tests/c/hip_stub_frames_pcm.cpp $(ROOT)/tests/c/hip_stub_frames_norm.cpp $(ROOT)/tests/c/hip_stub_rtc.cpp $(ROOT)/tests/c/engine_host_driver.cpp
+    $(ROOT)/tests/c/hip_stub_frames.cpp $(ROOT)/tests/c/hip_stub_frames_pcm.cpp $(ROOT)/tests/c/hip_stub_frames_norm.cpp $(ROOT)/tests/c/hip_stub_frames_fade.cpp $(ROOT)/tests/c/hip_stub_rtc.cpp $(ROOT)/tests/c/engine_host_driver.cpp
 ENGINE_FLAGS := -g -O1 -std=c++17 -Wall -Wno-unused-function -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -DRC_PMAX=32 \
     -I/opt/rocm/include -x c++
 ../../bin/engine_asan: $(ENGINE_SRC) ../rc_kernels.h ../rc_long.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
@@ -59,4 +59,10 @@ ENGINE_FRAMES_NORM_SRC := $(filter-out %/engine_host_driver.cpp,$(ENGINE_SRC)) $
 ../../bin/engine_frames_norm_asan: $(ENGINE_FRAMES_NORM_SRC) ../rc_kernels.h ../rc_long.h ../rc_frames.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
 	mkdir -p ../../bin
 	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(ENGINE_FLAGS) $(ENGINE_FRAMES_NORM_SRC) -o $@ -lpthread -ldl
+# ... and by tests/c/engine_host_driver_frames_fade.cpp: rc_engine_set_output_fade on the four whole-job host-form entries
+# (hip_stub_frames_fade.cpp's launcher logs its frame range and writes a mark over every sample of it)
+ENGINE_FRAMES_FADE_SRC := $(filter-out %/engine_host_driver.cpp,$(ENGINE_SRC)) $(ROOT)/tests/c/engine_host_driver_frames_fade.cpp
+../../bin/engine_frames_fade_asan: $(ENGINE_FRAMES_FADE_SRC) ../rc_kernels.h ../rc_long.h ../rc_frames.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
+	mkdir -p ../../bin
+	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(ENGINE_FLAGS) $(ENGINE_FRAMES_FADE_SRC) -o $@ -lpthread -ldl
 .PHONY: all

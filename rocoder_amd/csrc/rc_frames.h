@@ -101,11 +101,33 @@ struct FramesPackPcmGainParams {
     uint32_t store_gain;
 };
 
+// The output fade (rc_engine_set_output_fade; the definition is stated in include/rocoder_hip.h), in place on planar rows.
+// `planar` is the sample of the first channel at absolute output frame t0; the launch covers the frames [t0, t1) of every
+// channel, frame t of channel c at planar[c * stride + (t - t0)]. For each of them, with every operation ONE correctly
+// rounded IEEE f32 operation and the frame counts converted to f32 with round to nearest even:
+//   t < in_len                           x = x * up(t, in_len)
+//   out_start <= t < out_start + out_len x = x * down(t - out_start, out_len)   (after the line above: two multiplications
+//                                                                                 where the ranges overlap)
+//   t >= out_start + out_len             x = +0.0f, assigned: whatever x was, NaN included; x is not read
+//   up(p, d)   = sqrtf(0.5f * (1.0f + fmaxf( (p / d * 2.0f - 1.0f), -1.0f)))
+//   down(p, d) = sqrtf(0.5f * (1.0f + fmaxf(-(p / d * 2.0f - 1.0f), -1.0f)))
+// out_start == UINT64_MAX: no fade-out. out_start + out_len does not wrap (the engine's setter sees to it). A frame that
+// none of the three lines names is written back as it was read: the host launches on the frames a fade changes, each in
+// one launch only, so that every sample is read and written once.
+struct FramesFadeParams {
+    float *planar;
+    uint64_t stride;
+    uint32_t channels;
+    uint64_t in_len, out_start, out_len;
+    uint64_t t0, t1;
+};
+
 // (all: nothing is launched for n_frames == 0; a job of more than 2^27 frames goes out as several launches)
 hipError_t launch_frames_unpack(uint32_t format, const FramesUnpackParams &p, hipStream_t s);
 hipError_t launch_frames_pack(const FramesPackParams &p, hipStream_t s);
 hipError_t launch_frames_pack_pcm(uint32_t format, const FramesPackPcmParams &p, hipStream_t s);
 hipError_t launch_frames_peak(const FramesPeakParams &p, hipStream_t s);
 hipError_t launch_frames_pack_pcm_gain(uint32_t format, const FramesPackPcmGainParams &p, hipStream_t s);
+hipError_t launch_frames_fade(const FramesFadeParams &p, hipStream_t s);  // (nothing is launched for t1 <= t0)
 
 }  // namespace rc

@@ -371,6 +371,63 @@ __global__ __launch_bounds__(kFramesThreads) void frames_peak_kernel(FramesPeakP
     }
 }
 
+// ---- the output fade, in place on planar rows (rc_engine_set_output_fade; the definition: rc_frames.h) -----------------
+// The peak kernel's shape: a workgroup takes kFadeSegment samples of one row (blockIdx.y: the channel), 16-byte loads and
+// stores from the segment's first aligned address on, single dwords at its ragged ends. No two lanes share a sample.
+constexpr uint32_t kFadeSegment = 8192;
+
+// Position p of a fade of d frames, p < d. What makes every step one correctly rounded operation under this build:
+//   - the division and the square root by hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt (the v_div_scale /
+//     v_div_fmas / v_div_fixup sequence, v_sqrt_f32 with its correction step). Building with
+//     -fno-hip-fp32-correctly-rounded-divide-sqrt or fast-math breaks the definition.
+//   - the __f*_rn intrinsics are NOT a guard: in this toolchain's headers they are the plain operators unless
+//     OCML_BASIC_ROUNDED_OPERATIONS is defined (they state the intent, no more), and __fsqrt_rn is the hardware's 1-ulp
+//     approximation there, which is why the square root is sqrtf. Under -ffp-contract=fast the one fusable step is
+//     r * 2 - 1, and r * 2 is exact, so fused and unfused give the same bits; the additions and multiplications behind
+//     it feed a maximum, a square root or a store, which nothing fuses with.
+__device__ __forceinline__ float fade_gain(uint64_t p, uint64_t d, bool falling) {
+    const float r = __fdiv_rn(__ull2float_rn(p), __ull2float_rn(d));
+    const float b = __fsub_rn(__fmul_rn(r, 2.0f), 1.0f);
+    return sqrtf(__fmul_rn(0.5f, __fadd_rn(1.0f, fmaxf(falling ? -b : b, -1.0f))));
+}
+
+__device__ __forceinline__ bool fade_is_tail(uint64_t t, const FramesFadeParams &p) {
+    return t >= p.out_start && t - p.out_start >= p.out_len;
+}
+
+__device__ __forceinline__ float fade_sample(float x, uint64_t t, const FramesFadeParams &p) {
+    if (t < p.in_len) x = __fmul_rn(x, fade_gain(t, p.in_len, false));
+    if (t >= p.out_start) x = t - p.out_start < p.out_len ? __fmul_rn(x, fade_gain(t - p.out_start, p.out_len, true)) : 0.0f;
+    return x;
+}
+
+__global__ __launch_bounds__(kFramesThreads) void frames_fade_kernel(FramesFadeParams p) {
+    const uint32_t tid = threadIdx.x;
+    const uint64_t n = p.t1 - p.t0, s0 = (uint64_t)blockIdx.x * kFadeSegment;
+    if (s0 >= n) return;  // (the whole workgroup)
+    const uint32_t len = (uint32_t)(n - s0 < kFadeSegment ? n - s0 : kFadeSegment);
+    float *q = p.planar + (uint64_t)blockIdx.y * p.stride + s0;
+    const uint64_t t = p.t0 + s0;  // the frame of q[0]
+    const uint32_t head_want = (uint32_t)((16u - ((uintptr_t)q & 15u)) & 15u) >> 2, head = head_want < len ? head_want : len;
+    const uint32_t n4 = (len - head) >> 2;
+    if (tid < head) q[tid] = fade_sample(q[tid], t + tid, p);
+    float4 *q4 = (float4 *)(q + head);
+    for (uint32_t k = tid; k < n4; k += kFramesThreads) {
+        const uint64_t tk = t + head + 4u * k;
+        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (!fade_is_tail(tk, p)) {  // (behind the fade-out nothing is read: the group's later frames lie there too)
+            v = q4[k];
+            v.x = fade_sample(v.x, tk, p);
+            v.y = fade_sample(v.y, tk + 1, p);
+            v.z = fade_sample(v.z, tk + 2, p);
+            v.w = fade_sample(v.w, tk + 3, p);
+        }
+        q4[k] = v;
+    }
+    const uint32_t i = head + 4u * n4 + tid;  // (at most 3 behind the groups)
+    if (i < len) q[i] = fade_sample(q[i], t + i, p);
+}
+
 constexpr uint64_t kMaxFramesPerLaunch = (uint64_t)1 << 27;  // (a grid dimension times the block stays far below 2^32)
 
 // the launches after the first of a job of more than kMaxFramesPerLaunch frames: the gain is stored once
@@ -509,6 +566,23 @@ hipError_t launch_frames_pack_pcm_gain(uint32_t format, const FramesPackPcmGainP
     case PCM_I32: return pack_pcm_fmt<PCM_I32>(pp, s);
     default: return pack_pcm_fmt<PCM_F32>(pp, s);
     }
+}
+
+hipError_t launch_frames_fade(const FramesFadeParams &p, hipStream_t s) {
+    if (p.t1 <= p.t0) return hipSuccess;
+    if (!p.planar || p.channels == 0 || p.channels > 65535u || (p.out_start != UINT64_MAX && p.out_start + p.out_len < p.out_start))
+        return hipErrorInvalidValue;
+    for (uint64_t done = p.t0; done < p.t1; done += kMaxFramesPerLaunch) {
+        FramesFadeParams q = p;
+        q.planar = p.planar + (done - p.t0);
+        q.t0 = done;
+        q.t1 = p.t1 - done < kMaxFramesPerLaunch ? p.t1 : done + kMaxFramesPerLaunch;
+        const uint32_t segs = (uint32_t)((q.t1 - q.t0 + kFadeSegment - 1) / kFadeSegment);
+        frames_fade_kernel<<<dim3(segs, p.channels), dim3(kFramesThreads), 0, s>>>(q);
+        const hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
 }
 
 }  // namespace rc

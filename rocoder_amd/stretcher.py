@@ -535,6 +535,19 @@ class Engine:
         """compile_device_kernel + load_device_kernel."""
         self.load_device_kernel(compile_device_kernel(src, name))
 
+    def set_output_fade(self, fade_in: int = 0, fade_out_start: Optional[int] = None, fade_out_len: int = 0):
+        """The reference's sqrt fade-in over the first `fade_in` output frames and fade-out over `fade_out_len` frames
+        from frame `fade_out_start` on, zeros behind it (rc_engine_set_output_fade; the definition is in
+        include/rocoder_hip.h). Applied on the GPU by `stretch_host` and `stretch_frames` in front of the peak, the gain,
+        the quantiser and the clipped count; `stretch_device`, the streaming calls and MultiEngine are untouched.
+        `fade_out_start=None` is no fade-out, `fade_out_len=0` with a start a hard cut; the defaults clear the fade.
+        A call whose output is shorter than a fade raises (RC_EINVAL) and writes nothing."""
+        start = _lib.RC_FADE_NONE if fade_out_start is None else int(fade_out_start)
+        for v in (int(fade_in), start, int(fade_out_len)):
+            if not 0 <= v <= _lib.RC_FADE_NONE:
+                raise ValueError("fade frame counts are unsigned 64-bit integers")
+        self._check(self._L.rc_engine_set_output_fade(self._h, int(fade_in), start, int(fade_out_len)))
+
     def set_device_kernel_params(self, params: Sequence[float]):
         """Up to 16 floats, h.param(i) in the kernel; they take effect from the next call."""
         arr, n = _params_array(params)
