@@ -21,48 +21,41 @@ all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../b
 # streaming seam) host-only over tests/c/hip_stub.cpp - a HIP runtime whose device memory is host memory and whose
 # kernels compute nothing - driven by tests/c/engine_host_driver.cpp:
 #   ../../bin/engine_asan : -fsanitize=address,undefined      ../../bin/engine_tsan : -fsanitize=thread
-ENGINE_SRC := ../rc_engine.cpp ../rc_rtc.cpp $(ROOT)/tests/c/hip_stub.cpp $(ROOT)/tests/c/hip_stub_long.cpp \
-    $(ROOT)/tests/c/hip_stub_frames.cpp $(ROOT)/tests/c/hip_stub_frames_pcm.cpp $(ROOT)/tests/c/hip_stub_frames_norm.cpp $(ROOT)/tests/c/hip_stub_frames_fade.cpp $(ROOT)/tests/c/hip_stub_rtc.cpp $(ROOT)/tests/c/engine_host_driver.cpp
 ENGINE_FLAGS := -g -O1 -std=c++17 -Wall -Wno-unused-function -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -DRC_PMAX=32 \
     -I/opt/rocm/include -x c++
-../../bin/engine_asan: $(ENGINE_SRC) ../rc_kernels.h ../rc_long.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
+ASAN := -fsanitize=address,undefined -fno-sanitize-recover=undefined
+TSAN := -fsanitize=thread
+ENGINE_HDR := ../rc_kernels.h ../rc_long.h ../rc_frames.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
+# the engine and the stubs: compiled once per sanitizer, linked into every driver's program
+ENGINE_PARTS := rc_engine rc_rtc hip_stub hip_stub_long hip_stub_frames hip_stub_frames_pcm hip_stub_frames_norm \
+    hip_stub_frames_fade hip_stub_rtc
+ENGINE_ASAN_OBJ := $(ENGINE_PARTS:%=../../bin/%.asan.o)
+ENGINE_TSAN_OBJ := $(ENGINE_PARTS:%=../../bin/%.tsan.o)
+vpath %.cpp .. $(ROOT)/tests/c
+../../bin/%.asan.o: %.cpp $(ENGINE_HDR)
 	mkdir -p ../../bin
-	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(ENGINE_FLAGS) $(ENGINE_SRC) -o $@ -lpthread -ldl
-../../bin/engine_tsan: $(ENGINE_SRC) ../rc_kernels.h ../rc_long.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
+	$(CXX) $(ASAN) $(ENGINE_FLAGS) -c $< -o $@
+../../bin/%.tsan.o: %.cpp $(ENGINE_HDR)
 	mkdir -p ../../bin
-	$(CXX) -fsanitize=thread $(ENGINE_FLAGS) $(ENGINE_SRC) -o $@ -lpthread -ldl
-# the same engine build driven by tests/c/engine_host_driver_dk.cpp: a user device kernel with a history loaded
-ENGINE_DK_SRC := $(filter-out %/engine_host_driver.cpp,$(ENGINE_SRC)) $(ROOT)/tests/c/engine_host_driver_dk.cpp
-../../bin/engine_dk_asan: $(ENGINE_DK_SRC) ../rc_kernels.h ../rc_long.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
-	mkdir -p ../../bin
-	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(ENGINE_FLAGS) $(ENGINE_DK_SRC) -o $@ -lpthread -ldl
-# ... and by tests/c/engine_host_driver_xch.cpp: a user device kernel that reads the other channels loaded
-ENGINE_XCH_SRC := $(filter-out %/engine_host_driver.cpp,$(ENGINE_SRC)) $(ROOT)/tests/c/engine_host_driver_xch.cpp
-../../bin/engine_xch_asan: $(ENGINE_XCH_SRC) ../rc_kernels.h ../rc_long.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
-	mkdir -p ../../bin
-	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(ENGINE_FLAGS) $(ENGINE_XCH_SRC) -o $@ -lpthread -ldl
-# ... and by tests/c/engine_host_driver_frames.cpp: rc_engine_stretch_frames (hip_stub_frames.cpp's launchers read and
-# write exactly the byte and frame ranges the engine hands them)
-ENGINE_FRAMES_SRC := $(filter-out %/engine_host_driver.cpp,$(ENGINE_SRC)) $(ROOT)/tests/c/engine_host_driver_frames.cpp
-../../bin/engine_frames_asan: $(ENGINE_FRAMES_SRC) ../rc_kernels.h ../rc_long.h ../rc_frames.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
-	mkdir -p ../../bin
-	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(ENGINE_FLAGS) $(ENGINE_FRAMES_SRC) -o $@ -lpthread -ldl
-# ... and by tests/c/engine_host_driver_frames_pcm.cpp: rc_engine_stretch_frames_pcm (hip_stub_frames_pcm.cpp's launcher
-# writes exactly the bytes the real one may write, each marked with the sample it belongs to)
-ENGINE_FRAMES_PCM_SRC := $(filter-out %/engine_host_driver.cpp,$(ENGINE_SRC)) $(ROOT)/tests/c/engine_host_driver_frames_pcm.cpp
-../../bin/engine_frames_pcm_asan: $(ENGINE_FRAMES_PCM_SRC) ../rc_kernels.h ../rc_long.h ../rc_frames.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
-	mkdir -p ../../bin
-	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(ENGINE_FLAGS) $(ENGINE_FRAMES_PCM_SRC) -o $@ -lpthread -ldl
-# ... and by tests/c/engine_host_driver_frames_norm.cpp: rc_engine_stretch_frames_norm (hip_stub_frames_norm.cpp's peak
-# launcher counts the samples it covered, its pack launcher forms and stores the gain)
-ENGINE_FRAMES_NORM_SRC := $(filter-out %/engine_host_driver.cpp,$(ENGINE_SRC)) $(ROOT)/tests/c/engine_host_driver_frames_norm.cpp
-../../bin/engine_frames_norm_asan: $(ENGINE_FRAMES_NORM_SRC) ../rc_kernels.h ../rc_long.h ../rc_frames.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
-	mkdir -p ../../bin
-	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(ENGINE_FLAGS) $(ENGINE_FRAMES_NORM_SRC) -o $@ -lpthread -ldl
-# ... and by tests/c/engine_host_driver_frames_fade.cpp: rc_engine_set_output_fade on the four whole-job host-form entries
-# (hip_stub_frames_fade.cpp's launcher logs its frame range and writes a mark over every sample of it)
-ENGINE_FRAMES_FADE_SRC := $(filter-out %/engine_host_driver.cpp,$(ENGINE_SRC)) $(ROOT)/tests/c/engine_host_driver_frames_fade.cpp
-../../bin/engine_frames_fade_asan: $(ENGINE_FRAMES_FADE_SRC) ../rc_kernels.h ../rc_long.h ../rc_frames.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
-	mkdir -p ../../bin
-	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(ENGINE_FLAGS) $(ENGINE_FRAMES_FADE_SRC) -o $@ -lpthread -ldl
+	$(CXX) $(TSAN) $(ENGINE_FLAGS) -c $< -o $@
+.SECONDARY: $(ENGINE_ASAN_OBJ) $(ENGINE_TSAN_OBJ)
+../../bin/engine_asan: $(ROOT)/tests/c/engine_host_driver.cpp $(ENGINE_ASAN_OBJ) $(ENGINE_HDR)
+	$(CXX) $(ASAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_ASAN_OBJ) -o $@ -lpthread -ldl
+../../bin/engine_tsan: $(ROOT)/tests/c/engine_host_driver.cpp $(ENGINE_TSAN_OBJ) $(ENGINE_HDR)
+	$(CXX) $(TSAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_TSAN_OBJ) -o $@ -lpthread -ldl
+# the same engine build driven by tests/c/engine_host_driver_<name>.cpp:
+#   dk           a user device kernel with a history loaded
+#   xch          a user device kernel that reads the other channels loaded
+#   frames       rc_engine_stretch_frames (hip_stub_frames.cpp's launchers read and write exactly the byte and frame ranges
+#                the engine hands them)
+#   frames_pcm   rc_engine_stretch_frames_pcm (hip_stub_frames_pcm.cpp's launcher writes exactly the bytes the real one may
+#                write, each marked with the sample it belongs to)
+#   frames_norm  rc_engine_stretch_frames_norm (hip_stub_frames_norm.cpp's peak launcher counts the samples it covered, its
+#                pack launcher forms and stores the gain)
+#   frames_fade  rc_engine_set_output_fade on the four whole-job host-form entries (hip_stub_frames_fade.cpp's launcher logs
+#                its frame range and writes a mark over every sample of it)
+../../bin/engine_%_asan: $(ROOT)/tests/c/engine_host_driver_%.cpp $(ENGINE_ASAN_OBJ) $(ENGINE_HDR)
+	$(CXX) $(ASAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_ASAN_OBJ) -o $@ -lpthread -ldl
+../../bin/engine_%_tsan: $(ROOT)/tests/c/engine_host_driver_%.cpp $(ENGINE_TSAN_OBJ) $(ENGINE_HDR)
+	$(CXX) $(TSAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_TSAN_OBJ) -o $@ -lpthread -ldl
 .PHONY: all

@@ -29,13 +29,25 @@ def _build(target):
     return os.path.join(BIN, target)
 
 
+TSAN = {"TSAN_OPTIONS": "halt_on_error=0:second_deadlock_stack=1"}
+
+
+# (the frames drivers, tests/c/engine_host_driver_frames*.cpp, run the same worker pool with another task mix: raw frame
+# blocks up, packed blocks down, a run without downloads and one without uploads)
 @pytest.mark.parametrize("target,env,marker", [
     ("engine_asan", {"ASAN_OPTIONS": "detect_leaks=1", "UBSAN_OPTIONS": "print_stacktrace=1"}, "Sanitizer"),
     ("engine_tsan", {"TSAN_OPTIONS": "halt_on_error=0:second_deadlock_stack=1"}, "WARNING: ThreadSanitizer"),
+    ("engine_frames_tsan", TSAN, "WARNING: ThreadSanitizer"),
+    ("engine_frames_pcm_tsan", TSAN, "WARNING: ThreadSanitizer"),
+    ("engine_frames_norm_tsan", TSAN, "WARNING: ThreadSanitizer"),
+    ("engine_frames_fade_tsan", TSAN, "WARNING: ThreadSanitizer"),
 ])
 def test_engine_host_code_is_clean_under_sanitizers(target, env, marker):
     exe = _build(target)
     r = subprocess.run([exe], env=dict(os.environ, **env), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
     assert marker not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
-    assert r.stdout.startswith("OK engine host driver")
+    if target in ("engine_asan", "engine_tsan"):
+        assert r.stdout.startswith("OK engine host driver")
+    else:  # engine_<name>_tsan: the last line of tests/c/engine_host_driver_<name>.cpp
+        assert r.stdout.splitlines()[-1] == f"engine_host_driver_{target[len('engine_'):-len('_tsan')]}: ok", r.stdout[-500:]
