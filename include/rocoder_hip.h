@@ -263,6 +263,51 @@ int rc_engine_stretch_frames_norm(rc_engine *e, const void *frames, size_t n_fra
  * not. Only the frames a fade changes are touched: fades of 1 s cost 2 s of samples, not the job. */
 #define RC_FADE_NONE UINT64_MAX
 int rc_engine_set_output_fade(rc_engine *e, uint64_t in_len, uint64_t out_start, uint64_t out_len);
+/* The reference's autocrop (src/recorder.rs:146-191, applied to a recording in front of `-s/-d`, src/main.rs:173-181):
+ * the peak of every bin of a block of frames, measured on the device on the raw block, and the crop points those peaks
+ * give. Three entries; a caller cuts by pointer arithmetic - the frames entries above take frames at any byte alignment.
+ *
+ * rc_frames_power_bins: ceil(n_frames / bin_frames), the number of bins; 0 for bin_frames == 0. Pure host code.
+ *
+ * rc_engine_frames_power: chunked_audio_power (src/recorder.rs:94-113) on a block of n_frames frames of
+ * rc_config::channels channels in `format` (RC_PCM_*), at any byte alignment, as rc_engine_stretch_frames takes them. It
+ * returns LINEAR peaks, not decibels. The definition, bit for bit:
+ *   bin b    the frames [b * bin_frames, min((b + 1) * bin_frames, n_frames)), every channel; n_bins = ceil(n_frames /
+ *            bin_frames).
+ *   x        the reader's float of a sample, as stated for rc_engine_stretch_frames: (float)n / K, ONE correctly rounded
+ *            f32 division; RC_PCM_F32: the bits as they are.
+ *   peak[b]  the largest |x| over the bin's samples. NaN samples are skipped (the reference's partial_cmp().unwrap()
+ *            panics on one); +-inf counts and gives +inf; -0.0 is 0; denormals are kept. A bin of nothing but zeros or
+ *            NaN gives +0.0f.
+ * The block is uploaded in chunks and the kernel of a chunk runs under the upload of the next; page-locked memory
+ * (rc_host_alloc) is the DMA's source itself. The call blocks. It reads the engine's configuration (channels, device)
+ * and nothing else: the output fade, a loaded device kernel, the streaming state and the kernel-time ring are left as they
+ * were, and a stretch call behind it gives what it gave before. *n_bins is set whenever the arguments up to bin_frames
+ * are valid.
+ *   RC_EINVAL     a null pointer (`frames` may be null with n_frames == 0), a format outside 1 ... 5, bin_frames == 0
+ *   RC_ECAPACITY  bin_cap < n_bins (*n_bins is set)
+ *   n_frames == 0 is valid and gives *n_bins = 0.  On any error nothing behind bin_peak is written.
+ *
+ * rc_autocrop_points: determine_noise_threshold + determine_autocrop_points (src/recorder.rs:165-191) on those peaks, the
+ * reference as it stands. Pure host code: no device is touched, and it may be called from any thread.
+ *   dB[b]      max(log10f(|peak[b]|) * 20.0f, -99999999.0f) (power::relative_decibels, src/power.rs:6-8); the
+ *              comparisons below run on these values.
+ *   threshold  the value at index floor((float)percentile / 100.0f * (float)n_bins), computed in f32, of the sorted dB.
+ *   *start     the first frame of the first bin with dB > threshold.
+ *   *end       the first frame of the bin BEHIND the last bin with dB > threshold; where that last bin is the job's last
+ *              bin, its own first frame: the reference's `(last + 1).min(len - 1)`, reproduced, not mended.
+ *   The frames [*start, *end) are what remains. No bin above the threshold is the reference's None: *found = 0,
+ *   *start = 0, *end = n_frames, RC_OK. Otherwise *found = 1.
+ *   RC_EINVAL where the reference panics or asserts: a null pointer, n_bins == 0, percentile >= 100 or an index behind
+ *   the last bin, a NaN peak, bin_frames == 0, n_bins != rc_frames_power_bins(n_frames, bin_frames).
+ * Deviation: the reference converts its crop points to a Duration of f32 seconds and back (src/recorder.rs:155-162,
+ * src/audio.rs:132-138), which can move them by a frame in a long recording; this interface returns frames, and its
+ * callers cut at exactly those frames. */
+size_t rc_frames_power_bins(size_t n_frames, uint64_t bin_frames);
+int rc_engine_frames_power(rc_engine *e, const void *frames, size_t n_frames, uint32_t format, uint64_t bin_frames,
+                           float *bin_peak, size_t bin_cap, size_t *n_bins);
+int rc_autocrop_points(const float *bin_peak, size_t n_bins, uint64_t bin_frames, size_t n_frames, uint32_t percentile,
+                       uint64_t *start, uint64_t *end, int *found);
 /* Page-locked host memory for the host-form calls (the `Vec<f32>` a Rust host would otherwise hand over, src/main.rs:
  * 148, src/audio.rs:152-172): rows allocated here cross PCIe without a staging copy. rc_host_free(NULL) is a no-op.
  * RC_ENODEVICE without a GPU, RC_ENOMEM when the pages cannot be locked. */

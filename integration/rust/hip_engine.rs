@@ -89,6 +89,12 @@ extern "C" {
                                          target_peak: f32, out_frames_len: *mut usize, peak: *mut f32,
                                          gain: *mut f32, clipped: *mut u64) -> c_int;
     pub fn rc_engine_set_output_fade(e: *mut RcEngine, in_len: u64, out_start: u64, out_len: u64) -> c_int;  // RC_FADE_NONE = u64::MAX
+    // the reference's autocrop (src/recorder.rs:94-113,146-191): per-bin peaks of the raw block, then the crop points
+    pub fn rc_frames_power_bins(n_frames: usize, bin_frames: u64) -> usize;
+    pub fn rc_engine_frames_power(e: *mut RcEngine, frames: *const c_void, n_frames: usize, format: u32,
+                                  bin_frames: u64, bin_peak: *mut f32, bin_cap: usize, n_bins: *mut usize) -> c_int;
+    pub fn rc_autocrop_points(bin_peak: *const f32, n_bins: usize, bin_frames: u64, n_frames: usize,
+                              percentile: u32, start: *mut u64, end: *mut u64, found: *mut c_int) -> c_int;
     pub fn rc_host_alloc(bytes: usize, out: *mut *mut c_void) -> c_int;   // page-locked rows: no staging copy
     pub fn rc_host_free(p: *mut c_void) -> c_int;
     pub fn rc_engine_stretch_device(e: *mut RcEngine, d_in: *const f32, in_stride: usize, in_len: usize,

@@ -2,7 +2,7 @@
 overlap-add stretch path. The compute lives in librocoder_hip.so (hand-written HIP, C-ABI in
 include/rocoder_hip.h); this package is the host-side mirror of the reference interface."""
 from .stretcher import (AudioBus, AudioSpec, DeviceKernelCompileError, Engine, MultiEngine, ReFFT,  # noqa: F401
-                        RocoderError, Stretcher, StretcherProcessor, compile_device_kernel, derive_params,
+                        RocoderError, Stretcher, StretcherProcessor, autocrop_points, compile_device_kernel, derive_params,
                         device_kernel_cross_channel, device_kernel_history, load_kernel_library,
                         offline_output_len, pinned_empty, stretch)
 

@@ -183,6 +183,8 @@ struct FramesApi {
     decltype(&rc_engine_stretch_frames_pcm) stretch_pcm = nullptr;  // (--output-format only: may be missing)
     decltype(&rc_engine_stretch_frames_norm) stretch_norm = nullptr;  // (--normalize only: may be missing)
     decltype(&rc_engine_set_output_fade) set_fade = nullptr;  // (--fade-output only: may be missing)
+    decltype(&rc_engine_frames_power) power = nullptr;        // (--autocrop only: may be missing, both or neither)
+    decltype(&rc_autocrop_points) crop_points = nullptr;
     decltype(&rc_host_alloc) alloc = nullptr;
     decltype(&rc_host_free) free = nullptr;
 };
@@ -193,6 +195,8 @@ static const FramesApi &frames_api() {
         a.stretch_pcm = (decltype(a.stretch_pcm))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames_pcm");
         a.stretch_norm = (decltype(a.stretch_norm))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames_norm");
         a.set_fade = (decltype(a.set_fade))dlsym(RTLD_DEFAULT, "rc_engine_set_output_fade");
+        a.power = (decltype(a.power))dlsym(RTLD_DEFAULT, "rc_engine_frames_power");
+        a.crop_points = (decltype(a.crop_points))dlsym(RTLD_DEFAULT, "rc_autocrop_points");
         a.alloc = (decltype(a.alloc))dlsym(RTLD_DEFAULT, "rc_host_alloc");
         a.free = (decltype(a.free))dlsym(RTLD_DEFAULT, "rc_host_free");
         if (!a.stretch || !a.alloc || !a.free) throw std::runtime_error("--frames-on-gpu: the engine library has no rc_engine_stretch_frames");
@@ -1046,6 +1050,11 @@ struct Opt {  // src/main.rs:27-122
     std::optional<std::string> output_format;  // not in the reference (it writes f32): f32 | u8 | i16 | i24 | i32 | input
     bool frames_on_gpu = false;    // not in the reference: the file's frames are unpacked and the output interleaved on the GPU
     bool fade_output = false;      // not in the reference (it fades playback only): -x is applied to the output file, on the GPU (--frames-on-gpu)
+    // the reference crops what it records (recorder::autocrop_audio, src/recorder.rs:146-163, in front of -s/-d,
+    // src/main.rs:173-181); here it crops the file, measured on the GPU (--frames-on-gpu)
+    bool autocrop = false;
+    uint64_t autocrop_window_ms = 100;  // src/recorder.rs:15
+    uint32_t autocrop_percentile = 30;  // src/recorder.rs:16
     std::optional<float> normalize;  // not in the reference: the output's peak is brought to this level on the GPU (--frames-on-gpu)
 };
 
@@ -1070,6 +1079,10 @@ void usage() {
             "        --output-format <fmt>          Sample format of the output file: f32 | u8 | i16 | i24 | i32 | input (that of\n"
             "                                       the input file) [default: f32]. Integers are rounded to nearest and clipped;\n"
             "                                       the number of clipped samples is reported\n"
+            "        --autocrop                     With --frames-on-gpu: crop dead air off both ends of the input, as the reference\n"
+            "                                       crops a recording, in front of -s/-d; the peaks are measured on the GPU\n"
+            "        --autocrop-window <dur>        The analysis window of --autocrop [default: 0.1]\n"
+            "        --autocrop-percentile <p>      The noise-floor percentile of --autocrop, 0 ... 99 [default: 30]\n"
             "        --normalize <peak>             With --frames-on-gpu: measure the peak of the whole output on the GPU and scale\n"
             "                                       it to <peak> (1 = full scale) in front of the quantiser, any --output-format;\n"
             "                                       peak and gain are reported\n"
@@ -1166,6 +1179,19 @@ int run(int argc, char **argv) {
         else if (a == "--rotate-channels") o.rotate_channels = true;
         else if (a == "--frames-on-gpu") o.frames_on_gpu = true;
         else if (a == "--fade-output") o.fade_output = true;
+        else if (a == "--autocrop") o.autocrop = true;
+        else if (a == "--autocrop-window") {
+            o.autocrop_window_ms = dur(need(i));
+            if (o.autocrop_window_ms == 0) throw std::runtime_error("--autocrop-window takes a duration above 0");
+        }
+        else if (a == "--autocrop-percentile") {
+            const std::string v = need(i);
+            char *end = nullptr;
+            const unsigned long t = strtoul(v.c_str(), &end, 10);
+            if (v.empty() || *end || v[0] == '-' || t >= 100)
+                throw std::runtime_error("--autocrop-percentile takes an integer of 0 ... 99, not " + v);
+            o.autocrop_percentile = (uint32_t)t;
+        }
         else if (a == "--output-format") {
             o.output_format = need(i);
             if (!pcm_format_by_name(*o.output_format) && *o.output_format != "input")
@@ -1224,6 +1250,8 @@ int run(int argc, char **argv) {
     if (o.normalize && !o.frames_on_gpu) throw std::runtime_error("--normalize needs --frames-on-gpu");
     // (the fade is applied by the engine's whole-job calls: the streamed host writer has no such step)
     if (o.fade_output && !o.frames_on_gpu) throw std::runtime_error("--fade-output needs --frames-on-gpu");
+    // (the bins are measured by the engine on the raw frame block: the host reader has decoded it by then)
+    if (o.autocrop && !o.frames_on_gpu) throw std::runtime_error("--autocrop needs --frames-on-gpu");
     if (o.frames_on_gpu) {
         // one engine call computes the whole job: nothing polls a watched kernel between windows, and the frame block is
         // neither sharded nor reordered
@@ -1251,17 +1279,23 @@ int run(int argc, char **argv) {
     RawAudio raw;
     uint32_t in_format = RC_PCM_F32;
     size_t raw_first = 0, raw_count = 0;  // --frames-on-gpu: -s / -d as a frame offset and count into raw.data
+    // Audio::clip_in_place on the frames [raw_first, raw_first + raw_count): -s / -d inside what is there
+    auto clip_raw = [&]() {
+        if (!o.start_ms && !o.duration_ms) return;
+        const size_t have = raw_count;
+        size_t first = 0;
+        if (o.start_ms) first = (size_t)((double)*o.start_ms / 1000.0 * (double)raw.spec.sample_rate);
+        size_t endp = have;
+        if (o.duration_ms) endp = first + (size_t)((double)*o.duration_ms / 1000.0 * (double)raw.spec.sample_rate);
+        if (first > have || endp > have || first > endp)
+            throw std::runtime_error("clip range out of bounds (the reference panics on the slice)");
+        raw_first += first;
+        raw_count = endp - first;
+    };
     if (o.frames_on_gpu) {
         raw = read_wav_raw(f);
         raw_count = raw.frames;
-        if (o.start_ms || o.duration_ms) {  // Audio::clip_in_place
-            if (o.start_ms) raw_first = (size_t)((double)*o.start_ms / 1000.0 * (double)raw.spec.sample_rate);
-            size_t endp = raw.frames;
-            if (o.duration_ms) endp = raw_first + (size_t)((double)*o.duration_ms / 1000.0 * (double)raw.spec.sample_rate);
-            if (raw_first > raw.frames || endp > raw.frames || raw_first > endp)
-                throw std::runtime_error("clip range out of bounds (the reference panics on the slice)");
-            raw_count = endp - raw_first;
-        }
+        if (!o.autocrop) clip_raw();  // (with --autocrop: behind the crop, which needs the engine)
     } else {
         audio = read_wav(f, &in_format);
     }
@@ -1332,6 +1366,37 @@ int run(int argc, char **argv) {
         Engine eng;
         if (rc_engine_create(&cfg, &eng.h) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
         lap("engine create");
+        if (o.autocrop) {
+            // recorder::autocrop_audio on the whole file, then -s / -d inside what remains (src/main.rs:173-181): an offset
+            // and a count into the data chunk, no copy. The crop points are frames; the reference's round trip through a
+            // Duration of f32 seconds is left out.
+            if (!frames_api().power || !frames_api().crop_points)
+                throw std::runtime_error("--autocrop: the engine library has no rc_engine_frames_power");
+            const size_t bin_frames = (size_t)((float)((double)o.autocrop_window_ms / 1000.0) * (float)spec.sample_rate);  // duration_to_sample
+            if (bin_frames == 0) throw std::runtime_error("--autocrop-window is shorter than a frame");
+            if (raw.frames) {
+                const size_t n_bins = (raw.frames + bin_frames - 1) / bin_frames;
+                std::vector<float> peaks(n_bins);
+                size_t got = 0;
+                uint64_t start = 0, end = raw.frames;
+                int found = 0;
+                if (frames_api().power(eng.h, raw.data.p, raw.frames, raw.format, bin_frames, peaks.data(), n_bins, &got) != RC_OK ||
+                    frames_api().crop_points(peaks.data(), got, bin_frames, raw.frames, o.autocrop_percentile, &start, &end, &found) != RC_OK)
+                    throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+                if (found) {
+                    const double rate = (double)spec.sample_rate;
+                    fprintf(stderr, "autocropping audio to start %llu frames (%.6g s) later and end %llu frames (%.6g s) earlier\n",
+                            (unsigned long long)start, (double)start / rate, (unsigned long long)(raw.frames - end),
+                            (double)(raw.frames - end) / rate);
+                    raw_first = (size_t)start;
+                    raw_count = (size_t)(end - start);
+                } else {
+                    fprintf(stderr, "autocrop: no bin above the noise threshold, nothing cropped\n");
+                }
+            }
+            clip_raw();
+            lap("autocrop");
+        }
         const size_t cap = rc_offline_output_len(&cfg, raw_count);
         const uint32_t out_sb = pcm_sample_bytes(out_fmt);
         if (o.fade_output) {

@@ -122,6 +122,26 @@ struct FramesFadeParams {
     uint64_t t0, t1;
 };
 
+// The peak of every bin of a block of raw frames (rc_engine_frames_power; the definition is stated in
+// include/rocoder_hip.h). The block is what FramesUnpackParams describes: raw, raw_dwords, phase, channels, and the same
+// licence to load whole 16-byte groups around a range. The launch covers the job's frames [frame0, frame0 + n_frames),
+// a range that may start and end inside a bin, and adds to the bins it touches only:
+//   bin_bits[b] = max(bin_bits[b], bits of the largest |x| among the samples of the range in bin b), NaN skipped, +-inf
+//   kept, x the reader's float of the sample; bin b holds the frames [b * bin_frames, (b + 1) * bin_frames), every channel.
+// For non-negative floats the unsigned order of the bits is the order of the values, and a maximum does not depend on
+// the order: workgroups and launches join a bin with atomicMax. bin_bits holds n_bins words, zeroed by the host in front
+// of a job's first launch; the launcher refuses a range whose last frame lies in no bin of them.
+struct FramesPowerParams {
+    const uint32_t *raw;
+    uint64_t raw_dwords;
+    uint32_t phase;  // 0 ... 3
+    uint32_t channels;
+    uint64_t frame0, n_frames;
+    uint64_t bin_frames;  // >= 1
+    uint32_t *bin_bits;
+    uint64_t n_bins;
+};
+
 // (all: nothing is launched for n_frames == 0; a job of more than 2^27 frames goes out as several launches)
 hipError_t launch_frames_unpack(uint32_t format, const FramesUnpackParams &p, hipStream_t s);
 hipError_t launch_frames_pack(const FramesPackParams &p, hipStream_t s);
@@ -129,5 +149,6 @@ hipError_t launch_frames_pack_pcm(uint32_t format, const FramesPackPcmParams &p,
 hipError_t launch_frames_peak(const FramesPeakParams &p, hipStream_t s);
 hipError_t launch_frames_pack_pcm_gain(uint32_t format, const FramesPackPcmGainParams &p, hipStream_t s);
 hipError_t launch_frames_fade(const FramesFadeParams &p, hipStream_t s);  // (nothing is launched for t1 <= t0)
+hipError_t launch_frames_power(uint32_t format, const FramesPowerParams &p, hipStream_t s);
 
 }  // namespace rc

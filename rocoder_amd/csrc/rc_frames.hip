@@ -428,6 +428,111 @@ __global__ __launch_bounds__(kFramesThreads) void frames_fade_kernel(FramesFadeP
     if (i < len) q[i] = fade_sample(q[i], t + i, p);
 }
 
+// ---- the peak of every bin of a raw frame block (rc_engine_frames_power; the definition: include/rocoder_hip.h) ----------
+// A bin of bin_frames whole frames, every channel, is one contiguous range of the block's samples, so the kernel works on
+// the sample stream and never asks which channel a sample is: sample s of the job (s = frame * channels + channel) lies
+// in bin s / (bin_frames * channels). A workgroup takes kPowerTileBytes of the stream, whatever the channel count, through
+// LDS as the narrow unpack kernel does: 16-byte loads of the groups that cover the tile, a sample taken as the two dwords
+// it may straddle. What is reduced is a key that orders as |x| does - the magnitude of the integer, the bits of |x| for
+// f32 - and the float of the definition is formed once per partial result: n -> fl((float)|n| / K) is monotone, so the
+// largest key gives the largest |x|, bit for bit.
+//   a tile in one or two bins (a bin no shorter than the tile)   registers, __shfl_down, one atomicMax per bin
+//   a tile over more bins                                        an LDS word per bin, flushed with global atomics; above
+//                                                                kPowerLdsBins bins (bins of under a dozen samples) every
+//                                                                sample goes to its bin's global word itself
+constexpr uint32_t kPowerTileBytes = 12288;  // a multiple of every sample size
+constexpr uint32_t kPowerLdsDwords = (kPowerTileBytes / 16 + 2) * 4 + 4;
+constexpr uint32_t kPowerLdsBins = 1024;
+constexpr uint64_t kPowerMaxSamplesPerLaunch = (uint64_t)1 << 30;
+
+// orders as |x| does; 0 for a zero of either sign and for NaN (skipped). +-inf is kept: it sorts above every finite value.
+template <uint32_t FMT>
+__device__ __forceinline__ uint32_t power_key(uint32_t v) {
+    if (FMT == PCM_F32) {
+        const uint32_t b = v & 0x7fffffffu;
+        return b <= 0x7f800000u ? b : 0u;
+    }
+    const int32_t n = FMT == PCM_U8 ? (int32_t)(v & 0xffu) - 128 : FMT == PCM_I16 ? (int32_t)(int16_t)(v & 0xffffu)
+                    : FMT == PCM_I24 ? ((int32_t)(v << 8)) >> 8 : (int32_t)v;
+    return n < 0 ? 0u - (uint32_t)n : (uint32_t)n;  // (INT32_MIN: 2^31)
+}
+
+// the bits of |x| of the sample with that key: |(float)n / K| = (float)|n| / K, conversion and division rounded to nearest
+template <uint32_t FMT>
+__device__ __forceinline__ uint32_t power_bits(uint32_t key) {
+    if (FMT == PCM_F32) return key;
+    constexpr float K = FMT == PCM_U8 ? 127.0f : FMT == PCM_I16 ? 32767.0f : FMT == PCM_I24 ? 8388608.0f : 2147483647.0f;
+    return __float_as_uint(__uint2float_rn(key) / K);
+}
+
+template <uint32_t FMT>
+__global__ __launch_bounds__(kFramesThreads) void frames_power_kernel(FramesPowerParams p) {
+    constexpr uint32_t B = fmt_bytes<FMT>(), TS = kPowerTileBytes / B;
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kPowerLdsDwords];
+    __shared__ uint32_t bins[kPowerLdsBins];
+    __shared__ uint32_t wave_max[2][kWaves];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t s_end = (p.frame0 + p.n_frames) * p.channels;
+    const uint64_t s0 = p.frame0 * p.channels + (uint64_t)blockIdx.x * TS;
+    if (s0 >= s_end) return;  // (the whole workgroup)
+    const uint32_t ts = (uint32_t)(s_end - s0 < TS ? s_end - s0 : TS);
+    const uint64_t b0 = p.phase + s0 * B, b1 = b0 + (uint64_t)ts * B;
+    const uint64_t g0 = b0 >> 4, g1 = (b1 + 15) >> 4;  // 16-byte groups [g0, g1): at most 769
+    const uint4 *raw4 = (const uint4 *)p.raw;
+    const uint64_t raw_groups = p.raw_dwords >> 2;
+    for (uint32_t g = tid; g < (uint32_t)(g1 - g0); g += kFramesThreads) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (g0 + g < raw_groups) v = raw4[g0 + g];
+        ((uint4 *)lds)[g] = v;
+    }
+    const uint32_t lead = (uint32_t)(b0 - (g0 << 4));  // bytes of the first group in front of the tile
+    const uint64_t bs = p.bin_frames * p.channels;     // samples of a bin
+    const uint64_t bin_a = s0 / bs, n_touched = (s0 + ts - 1) / bs - bin_a + 1;
+    if (n_touched <= 2) {
+        // samples [0, edge) of the tile lie in bin_a, the rest in the bin behind it
+        const uint32_t edge = n_touched == 2 ? (uint32_t)((bin_a + 1) * bs - s0) : ts;
+        __syncthreads();
+        uint32_t m0 = 0, m1 = 0;
+        for (uint32_t i = tid; i < ts; i += kFramesThreads) {
+            const uint32_t k = power_key<FMT>(lds_bits(lds, lead + i * B));
+            if (i < edge) m0 = max(m0, k);
+            else m1 = max(m1, k);
+        }
+        for (uint32_t off = 32; off; off >>= 1) {
+            m0 = max(m0, (uint32_t)__shfl_down(m0, off));
+            m1 = max(m1, (uint32_t)__shfl_down(m1, off));
+        }
+        if ((tid & 63u) == 0) {
+            wave_max[0][tid >> 6] = m0;
+            wave_max[1][tid >> 6] = m1;
+        }
+        __syncthreads();
+        if (tid < 2) {  // (thread 0: bin_a, thread 1: the bin behind it)
+            uint32_t m = 0;
+            for (uint32_t w = 0; w < kWaves; ++w) m = max(m, wave_max[tid][w]);
+            if (m) atomicMax(&p.bin_bits[bin_a + tid], power_bits<FMT>(m));
+        }
+        return;
+    }
+    // more than two bins: a bin is shorter than the tile, so a bin's length and the tile's offset in bin_a are small
+    const uint32_t nb = (uint32_t)n_touched, bs32 = (uint32_t)bs, r0 = (uint32_t)(s0 - bin_a * bs);
+    const bool in_lds = nb <= kPowerLdsBins;
+    if (in_lds)
+        for (uint32_t i = tid; i < nb; i += kFramesThreads) bins[i] = 0;
+    __syncthreads();
+    for (uint32_t i = tid; i < ts; i += kFramesThreads) {
+        const uint32_t k = power_key<FMT>(lds_bits(lds, lead + i * B));
+        if (!k) continue;
+        const uint32_t rel = (r0 + i) / bs32;
+        if (in_lds) atomicMax(&bins[rel], k);
+        else atomicMax(&p.bin_bits[bin_a + rel], power_bits<FMT>(k));
+    }
+    if (!in_lds) return;
+    __syncthreads();
+    for (uint32_t i = tid; i < nb; i += kFramesThreads)
+        if (bins[i]) atomicMax(&p.bin_bits[bin_a + i], power_bits<FMT>(bins[i]));
+}
+
 constexpr uint64_t kMaxFramesPerLaunch = (uint64_t)1 << 27;  // (a grid dimension times the block stays far below 2^32)
 
 // the launches after the first of a job of more than kMaxFramesPerLaunch frames: the gain is stored once
@@ -479,6 +584,24 @@ hipError_t unpack_fmt(const FramesUnpackParams &p, hipStream_t s) {
             const uint32_t ct = (p.channels + kWideChannels - 1) / kWideChannels;
             frames_unpack_wide_kernel<FMT><<<dim3(tiles, ct), dim3(kFramesThreads), 0, s>>>(q);
         }
+        const hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
+template <uint32_t FMT>
+hipError_t power_fmt(const FramesPowerParams &p, hipStream_t s) {
+    constexpr uint32_t TS = kPowerTileBytes / fmt_bytes<FMT>();
+    // (a launch: at most 2^27 frames and at most 2^30 samples, whichever is fewer; at least one frame)
+    const uint64_t by_samples = kPowerMaxSamplesPerLaunch / p.channels;
+    const uint64_t per = by_samples < kMaxFramesPerLaunch ? (by_samples ? by_samples : 1) : kMaxFramesPerLaunch;
+    for (uint64_t done = 0; done < p.n_frames; done += per) {
+        FramesPowerParams q = p;
+        q.frame0 = p.frame0 + done;
+        q.n_frames = p.n_frames - done < per ? p.n_frames - done : per;
+        const uint32_t tiles = (uint32_t)((q.n_frames * p.channels + TS - 1) / TS);
+        frames_power_kernel<FMT><<<dim3(tiles), dim3(kFramesThreads), 0, s>>>(q);
         const hipError_t err = hipGetLastError();
         if (err != hipSuccess) return err;
     }
@@ -583,6 +706,28 @@ hipError_t launch_frames_fade(const FramesFadeParams &p, hipStream_t s) {
         if (err != hipSuccess) return err;
     }
     return hipSuccess;
+}
+
+hipError_t launch_frames_power(uint32_t format, const FramesPowerParams &pp, hipStream_t s) {
+    if (!pcm_bytes(format)) return hipErrorInvalidValue;
+    if (pp.n_frames == 0) return hipSuccess;
+    if (pp.channels == 0 || pp.channels > 65535u || pp.phase > 3u || (pp.raw_dwords & 3u) || ((uintptr_t)pp.raw & 15u) || !pp.bin_bits ||
+        pp.bin_frames == 0 || pp.frame0 + pp.n_frames < pp.frame0)
+        return hipErrorInvalidValue;
+    FramesPowerParams p = pp;
+    // every frame of the range lies in front of frame0 + n_frames: a longer bin holds the same frames, and the kernel's
+    // samples of a bin (bin_frames x channels) stay far inside 64 bits
+    if (p.bin_frames > p.frame0 + p.n_frames) p.bin_frames = p.frame0 + p.n_frames;
+    if ((p.frame0 + p.n_frames - 1) / p.bin_frames >= p.n_bins) return hipErrorInvalidValue;  // a bin behind bin_bits
+    // the range's last byte lies inside raw
+    if ((p.phase + (p.frame0 + p.n_frames) * p.channels * pcm_bytes(format) + 3) / 4 > p.raw_dwords) return hipErrorInvalidValue;
+    switch (format) {
+    case PCM_U8: return power_fmt<PCM_U8>(p, s);
+    case PCM_I16: return power_fmt<PCM_I16>(p, s);
+    case PCM_I24: return power_fmt<PCM_I24>(p, s);
+    case PCM_I32: return power_fmt<PCM_I32>(p, s);
+    default: return power_fmt<PCM_F32>(p, s);
+    }
 }
 
 }  // namespace rc

@@ -212,6 +212,23 @@ def offline_output_len(in_len: int, **kw) -> int:
     return int(_lib.lib().rc_offline_output_len(C.byref(cfg), in_len))
 
 
+def autocrop_points(bin_peak, bin_frames: int, n_frames: int, percentile: int = 30):
+    """The reference's crop points (determine_noise_threshold + determine_autocrop_points, src/recorder.rs:165-191) from
+    the peaks `Engine.frames_power` gives: (start, end) in frames - the job's frames [start, end) are what remains - or
+    None where no bin lies above the threshold (the reference crops nothing then). The comparisons run on decibels, the
+    threshold is the value at index floor(percentile / 100 * n_bins) of the sorted bins, and `end` is the first frame of
+    the bin behind the last one above the threshold - of that bin itself where it is the job's last (the reference's
+    quirk, kept). Pure host code (rc_autocrop_points): no device is touched."""
+    peaks = np.ascontiguousarray(bin_peak, np.float32).reshape(-1)
+    start, end, found = C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+    if not (0 <= int(percentile) < 2 ** 32 and 0 <= int(bin_frames) < 2 ** 64 and int(n_frames) >= 0):
+        raise ValueError("percentile, bin_frames and n_frames are unsigned integers")
+    L = _lib.lib()
+    check(L.rc_autocrop_points(_fp(peaks), peaks.size, int(bin_frames), int(n_frames), int(percentile), C.byref(start),
+                               C.byref(end), C.byref(found)), L)
+    return (int(start.value), int(end.value)) if found.value else None
+
+
 class _ViewOwner:
     """`base` of the arrays next_window_view hands out: keeps the engine alive and knows whether it is still current."""
 
@@ -371,6 +388,30 @@ class Engine:
     last_peak: Optional[float] = None   # stretch_frames(normalize=...): the largest finite |sample| before the gain ...
     last_gain: Optional[float] = None   # ... and the gain it was multiplied by (both np.float32)
 
+    def _raw_frames(self, frames, fmt):
+        """What `stretch_frames` documents for `frames` and `fmt` -> (the block's bytes, the RC_PCM_* code, n_frames)."""
+        by_dtype = {"uint8": "u8", "int16": "i16", "int32": "i32", "float32": "f32"}
+        if fmt is None:
+            a = np.asarray(frames)
+            if a.dtype.name not in by_dtype or a.ndim != 2:
+                raise ValueError("frames must be [n_frames, channels] uint8 / int16 / int32 / float32, or bytes with fmt=")
+            fmt = by_dtype[a.dtype.name]
+            if a.shape[1] != self.channels:
+                raise ValueError("channel count mismatch")
+        elif fmt not in _lib.PCM_FORMATS:
+            raise ValueError(f"fmt must be one of {sorted(_lib.PCM_FORMATS)}")
+        else:
+            a = np.frombuffer(frames, np.uint8) if isinstance(frames, (bytes, bytearray, memoryview)) else np.asarray(frames)
+        code = _lib.PCM_FORMATS[fmt]
+        if not a.flags.c_contiguous:
+            a = np.ascontiguousarray(a)
+        raw = a.reshape(-1).view(np.uint8)
+        frame_bytes = _lib.PCM_BYTES[code] * self.channels
+        if raw.size % frame_bytes:
+            raise ValueError(f"{raw.size} bytes are no whole number of {frame_bytes}-byte frames")
+        n = raw.size // frame_bytes
+        return raw, code, n
+
     def stretch_frames(self, frames, fmt: Optional[str] = None, out: Optional[np.ndarray] = None,
                        out_fmt: Optional[str] = None, normalize: Optional[float] = None) -> np.ndarray:
         """Interleaved PCM frames in, interleaved float32 frames out (rc_engine_stretch_frames): both format changes run
@@ -398,26 +439,7 @@ class Engine:
                 raise ValueError("normalize must be a finite float32 above 0")
             if out_fmt is None:
                 out_fmt = "f32"
-        by_dtype = {"uint8": "u8", "int16": "i16", "int32": "i32", "float32": "f32"}
-        if fmt is None:
-            a = np.asarray(frames)
-            if a.dtype.name not in by_dtype or a.ndim != 2:
-                raise ValueError("frames must be [n_frames, channels] uint8 / int16 / int32 / float32, or bytes with fmt=")
-            fmt = by_dtype[a.dtype.name]
-            if a.shape[1] != self.channels:
-                raise ValueError("channel count mismatch")
-        elif fmt not in _lib.PCM_FORMATS:
-            raise ValueError(f"fmt must be one of {sorted(_lib.PCM_FORMATS)}")
-        else:
-            a = np.frombuffer(frames, np.uint8) if isinstance(frames, (bytes, bytearray, memoryview)) else np.asarray(frames)
-        code = _lib.PCM_FORMATS[fmt]
-        if not a.flags.c_contiguous:
-            a = np.ascontiguousarray(a)
-        raw = a.reshape(-1).view(np.uint8)
-        frame_bytes = _lib.PCM_BYTES[code] * self.channels
-        if raw.size % frame_bytes:
-            raise ValueError(f"{raw.size} bytes are no whole number of {frame_bytes}-byte frames")
-        n = raw.size // frame_bytes
+        raw, code, n = self._raw_frames(frames, fmt)
         n_out = self.output_len(n)
         if out_fmt is not None:
             if out_fmt not in _lib.PCM_FORMATS:
@@ -456,6 +478,24 @@ class Engine:
         self._check(self._L.rc_engine_stretch_frames(self._h, src, n, code, _fp(out), out.shape[0], C.byref(got)))
         assert got.value == n_out
         return out[:n_out]
+
+    def frames_power(self, frames, fmt: Optional[str] = None, bin_frames: int = 4410) -> np.ndarray:
+        """The peak of every bin of `bin_frames` whole frames of a block of interleaved PCM frames, measured on the GPU
+        on the raw block (rc_engine_frames_power): float32 [ceil(n_frames / bin_frames)], the largest |x| over all
+        channels of the bin, x the reader's float of a sample, NaN samples skipped; linear, not decibels. `frames` and
+        `fmt` are `stretch_frames`'s. It is the reference's `chunked_audio_power` (src/recorder.rs:94-113), the input of
+        `autocrop_points`. The engine's fade, kernels and streaming state are left as they were."""
+        bin_frames = int(bin_frames)
+        if not 1 <= bin_frames < 2 ** 64:
+            raise ValueError("bin_frames must be an integer of 1 ... 2^64 - 1")
+        raw, code, n = self._raw_frames(frames, fmt)
+        n_bins = int(self._L.rc_frames_power_bins(n, bin_frames))
+        out = np.empty(max(n_bins, 1), np.float32)
+        got = C.c_size_t(0)
+        src = C.c_void_p(raw.ctypes.data if raw.size else out.ctypes.data)  # (no frames: any non-null pointer)
+        self._check(self._L.rc_engine_frames_power(self._h, src, n, code, bin_frames, _fp(out), n_bins, C.byref(got)))
+        assert got.value == n_bins
+        return out[:n_bins]
 
     def stretch_device_ptr(self, d_in: int, in_stride: int, in_len: int, d_out: int, out_stride: int,
                            out_cap: int, stream: int = 0) -> int:
