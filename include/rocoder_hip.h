@@ -308,6 +308,56 @@ int rc_engine_frames_power(rc_engine *e, const void *frames, size_t n_frames, ui
                            float *bin_peak, size_t bin_cap, size_t *n_bins);
 int rc_autocrop_points(const float *bin_peak, size_t n_bins, uint64_t bin_frames, size_t n_frames, uint32_t percentile,
                        uint64_t *start, uint64_t *end, int *found);
+/* The reference's channel treatment of its input on the frames path: Audio::rotate_channels (src/audio.rs:73-75), any
+ * other permutation or copy of channels, and recorder::auto_split_mono (src/recorder.rs:118-144). Three entries.
+ *
+ * rc_engine_set_channel_map: which channel of the frame block each row of a frames job reads. The map is engine state, set
+ * once, like the output fade: map == NULL or n == 0 clears it, and that is the state after rc_engine_create. Otherwise n
+ * must equal rc_config::channels and every map[c] < channels: if not, RC_EINVAL, and the previous map stays. While a map
+ * is set, row c of the job reads channel map[c] of the block; a source channel may feed several rows, or none. It
+ * applies to rc_engine_stretch_frames, rc_engine_stretch_frames_pcm and rc_engine_stretch_frames_norm, the path those
+ * three take under a host frequency kernel (rc_config::kernel) included. The definition, one sentence: the entry
+ * returns exactly what it returns, with no map set, on the block whose frame f holds at channel c the sample
+ * (f, map[c]) of the given block - every output byte in every output format, *clipped, *peak and *gain, with the fade
+ * and a loaded user or curated device kernel downstream as before. The block still holds `channels` samples per frame,
+ * and nothing in it is written. An identity map gives what no map gives (the engine takes the unmapped launches for it).
+ * The rotation of `--rotate-channels` is map[c] = (c + channels - 1) % channels (rotate_right(1); stereo: {1, 0}).
+ * The map does NOT apply to rc_engine_stretch_host (a caller permutes its row pointers itself), to the device forms, to
+ * the streaming seam, to rc_multi, to rc_engine_frames_power or to rc_engine_frames_channel_peaks: they read what they
+ * read, map set or not. For rc_engine_frames_power that is still the reference's result: a bin's peak is the maximum over
+ * all channels, which no permutation changes and which copying the loudest channel over silent ones does not change
+ * either, so autocropping the raw block equals autocropping after auto_split_mono.
+ *
+ * rc_engine_frames_channel_peaks: the measurement behind `channel_data.iter().all(|s| *s == 0.0)` (src/recorder.rs:122),
+ * on the raw block of n_frames frames of rc_config::channels channels in `format` (RC_PCM_*), at any byte alignment, as
+ * rc_engine_stretch_frames takes them. The definition, bit for bit:
+ *   x             the reader's float of a sample, as stated for rc_engine_stretch_frames: (float)n / K, ONE correctly
+ *                 rounded f32 division; RC_PCM_F32: the bits as they are.
+ *   chan_peak[c]  for c < channels, the float whose bits are the unsigned maximum of the bits of |x| (the sign bit
+ *                 cleared) over the samples of channel c.
+ * So a NaN sample wins over everything - deliberately, and unlike the bin peaks of rc_engine_frames_power, which skip
+ * NaN: in the reference `NaN == 0.0` is false, and such a channel is not silent. Otherwise +-inf gives +inf; otherwise
+ * the result is the largest finite magnitude. Denormals are kept; -0.0 gives +0.0. chan_peak[c] == 0.0f exactly when the
+ * reference's test holds for channel c. n_frames == 0 is valid and gives +0.0f for every channel.
+ *   RC_EINVAL     a null pointer (`frames` may be null with n_frames == 0), a format outside 1 ... 5
+ *   RC_ECAPACITY  cap < channels
+ *   On any error nothing behind chan_peak is written.
+ * The call blocks. Like rc_engine_frames_power it leaves the engine as it was: the output fade, a loaded device kernel,
+ * the streaming state, the kernel-time ring and the channel map itself are untouched. It is chunked like
+ * rc_engine_frames_power: the kernel of a chunk runs under the upload of the next, and page-locked memory (rc_host_alloc)
+ * is the DMA's source itself.
+ *
+ * rc_split_mono_map: the decision of auto_split_mono (src/recorder.rs:118-144) as it stands, on those peaks. Pure host
+ * code: no device is touched, and it may be called from any thread. Channel c is empty where chan_peak[c] == 0.0f (a NaN
+ * peak is not empty). Where exactly channels - 1 channels are empty and one is not - the reference's
+ * last_nonempty_channel, m - map[c] = m for every c and *found = 1; that includes channels == 1 with a non-silent
+ * channel, where the reference's condition holds too and the map is the identity. Otherwise the identity map and
+ * *found = 0. RC_EINVAL: a null pointer, or channels == 0. `map` holds `channels` words; it is what
+ * rc_engine_set_channel_map takes. */
+int rc_engine_set_channel_map(rc_engine *e, const uint32_t *map, uint32_t n);
+int rc_engine_frames_channel_peaks(rc_engine *e, const void *frames, size_t n_frames, uint32_t format, float *chan_peak,
+                                   size_t cap);
+int rc_split_mono_map(const float *chan_peak, uint32_t channels, uint32_t *map, int *found);
 /* Page-locked host memory for the host-form calls (the `Vec<f32>` a Rust host would otherwise hand over, src/main.rs:
  * 148, src/audio.rs:152-172): rows allocated here cross PCIe without a staging copy. rc_host_free(NULL) is a no-op.
  * RC_ENODEVICE without a GPU, RC_ENOMEM when the pages cannot be locked. */

@@ -95,6 +95,12 @@ extern "C" {
                                   bin_frames: u64, bin_peak: *mut f32, bin_cap: usize, n_bins: *mut usize) -> c_int;
     pub fn rc_autocrop_points(bin_peak: *const f32, n_bins: usize, bin_frames: u64, n_frames: usize,
                               percentile: u32, start: *mut u64, end: *mut u64, found: *mut c_int) -> c_int;
+    // rotate_channels / auto_split_mono on the frames path (src/audio.rs:73-75, src/recorder.rs:118-144): row c of a frames
+    // job reads channel map[c]; per-channel peaks of the raw block; the split-mono decision
+    pub fn rc_engine_set_channel_map(e: *mut RcEngine, map: *const u32, n: u32) -> c_int;  // null or n == 0 clears it
+    pub fn rc_engine_frames_channel_peaks(e: *mut RcEngine, frames: *const c_void, n_frames: usize, format: u32,
+                                          chan_peak: *mut f32, cap: usize) -> c_int;
+    pub fn rc_split_mono_map(chan_peak: *const f32, channels: u32, map: *mut u32, found: *mut c_int) -> c_int;
     pub fn rc_host_alloc(bytes: usize, out: *mut *mut c_void) -> c_int;   // page-locked rows: no staging copy
     pub fn rc_host_free(p: *mut c_void) -> c_int;
     pub fn rc_engine_stretch_device(e: *mut RcEngine, d_in: *const f32, in_stride: usize, in_len: usize,

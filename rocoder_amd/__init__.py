@@ -4,6 +4,6 @@ include/rocoder_hip.h); this package is the host-side mirror of the reference in
 from .stretcher import (AudioBus, AudioSpec, DeviceKernelCompileError, Engine, MultiEngine, ReFFT,  # noqa: F401
                         RocoderError, Stretcher, StretcherProcessor, autocrop_points, compile_device_kernel, derive_params,
                         device_kernel_cross_channel, device_kernel_history, load_kernel_library,
-                        offline_output_len, pinned_empty, stretch)
+                        offline_output_len, pinned_empty, split_mono_map, stretch)
 
 __version__ = "0.1.0"

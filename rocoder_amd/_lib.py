@@ -117,6 +117,9 @@ SYMBOLS = {
                                          C.POINTER(_sz)]),
     "rc_autocrop_points": (C.c_int, [C.POINTER(C.c_float), _sz, C.c_uint64, _sz, C.c_uint32, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "rc_engine_set_channel_map": (C.c_int, [_eng, C.POINTER(C.c_uint32), C.c_uint32]),
+    "rc_engine_frames_channel_peaks": (C.c_int, [_eng, C.c_void_p, _sz, C.c_uint32, C.POINTER(C.c_float), _sz]),
+    "rc_split_mono_map": (C.c_int, [C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "rc_host_alloc": (C.c_int, [_sz, C.POINTER(C.c_void_p)]),
     "rc_host_free": (C.c_int, [C.c_void_p]),
     "rc_engine_stretch_device": (C.c_int, [_eng, C.c_void_p, _sz, _sz, C.c_void_p, _sz, _sz,

@@ -14,6 +14,7 @@
 #include <unistd.h>
 
 #include <atomic>
+#include <cctype>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -22,6 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <optional>
@@ -185,6 +187,9 @@ struct FramesApi {
     decltype(&rc_engine_set_output_fade) set_fade = nullptr;  // (--fade-output only: may be missing)
     decltype(&rc_engine_frames_power) power = nullptr;        // (--autocrop only: may be missing, both or neither)
     decltype(&rc_autocrop_points) crop_points = nullptr;
+    decltype(&rc_engine_set_channel_map) set_map = nullptr;  // (--channel-map / --split-mono only: may be missing)
+    decltype(&rc_engine_frames_channel_peaks) channel_peaks = nullptr;  // (--split-mono only: may be missing, both or neither)
+    decltype(&rc_split_mono_map) split_map = nullptr;
     decltype(&rc_host_alloc) alloc = nullptr;
     decltype(&rc_host_free) free = nullptr;
 };
@@ -197,6 +202,9 @@ static const FramesApi &frames_api() {
         a.set_fade = (decltype(a.set_fade))dlsym(RTLD_DEFAULT, "rc_engine_set_output_fade");
         a.power = (decltype(a.power))dlsym(RTLD_DEFAULT, "rc_engine_frames_power");
         a.crop_points = (decltype(a.crop_points))dlsym(RTLD_DEFAULT, "rc_autocrop_points");
+        a.set_map = (decltype(a.set_map))dlsym(RTLD_DEFAULT, "rc_engine_set_channel_map");
+        a.channel_peaks = (decltype(a.channel_peaks))dlsym(RTLD_DEFAULT, "rc_engine_frames_channel_peaks");
+        a.split_map = (decltype(a.split_map))dlsym(RTLD_DEFAULT, "rc_split_mono_map");
         a.alloc = (decltype(a.alloc))dlsym(RTLD_DEFAULT, "rc_host_alloc");
         a.free = (decltype(a.free))dlsym(RTLD_DEFAULT, "rc_host_free");
         if (!a.stretch || !a.alloc || !a.free) throw std::runtime_error("--frames-on-gpu: the engine library has no rc_engine_stretch_frames");
@@ -233,12 +241,18 @@ struct RawAudio {
     PinnedBytes data;
     size_t frames = 0;
 };
-RawAudio read_wav_raw(FILE *f) {
+// an argument that does not fit the input file: one error line and exit status 2, before any engine work
+struct UsageError : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+// `on_header`: called with the file's spec once the header is read, in front of the data chunk and its allocation
+RawAudio read_wav_raw(FILE *f, const std::function<void(const AudioSpec &)> &on_header = {}) {
     const WavHeader h = read_wav_header(f);
     check_wav_format(h);
     RawAudio a;
     a.spec.channels = h.channels;
     a.spec.sample_rate = h.rate;
+    if (on_header) on_header(a.spec);
     a.sample_bytes = h.bits / 8u;
     a.format = h.fmt_tag == 3 ? RC_PCM_F32 : h.bits == 8 ? RC_PCM_U8 : h.bits == 16 ? RC_PCM_I16 : h.bits == 24 ? RC_PCM_I24 : RC_PCM_I32;
     size_t got = 0;
@@ -1055,15 +1069,24 @@ struct Opt {  // src/main.rs:27-122
     bool autocrop = false;
     uint64_t autocrop_window_ms = 100;  // src/recorder.rs:15
     uint32_t autocrop_percentile = 30;  // src/recorder.rs:16
+    // Audio::rotate_channels (src/audio.rs:73-75) and any other permutation or copy of channels under --frames-on-gpu: row c
+    // of the job reads channel channel_map[c] of the file, in the GPU's unpack kernel
+    std::optional<std::vector<uint32_t>> channel_map;
+    // recorder::auto_split_mono (src/recorder.rs:118-144, in front of the autocrop, :64-70): measured on the GPU (--frames-on-gpu)
+    bool split_mono = false;
     std::optional<float> normalize;  // not in the reference: the output's peak is brought to this level on the GPU (--frames-on-gpu)
 };
 
 void usage() {
     fprintf(stderr,
             "rocoder (gfx950 engine)\nA live-codeable phase vocoder.\n\nUSAGE:\n    rocoder [FLAGS] [OPTIONS]\n\n"
-            "FLAGS:\n        --rotate-channels    Rotate the input audio channels\n"
+            "FLAGS:\n        --rotate-channels    Rotate the input audio channels (with --frames-on-gpu: spelled --channel-map,\n"
+            "                             stereo --channel-map 1,0; in general map[c] = (c + C - 1) %% C)\n"
             "        --frames-on-gpu      Decode the input's PCM frames and interleave the output on the GPU (one engine call;\n"
             "                             not with --freq-kernel, --device-kernel-src, --devices, --rotate-channels)\n"
+            "        --split-mono         With --frames-on-gpu: where all channels of the input but one are silent, copy that\n"
+            "                             channel over the others, as the reference treats a mono source recorded from a\n"
+            "                             non-mono device, in front of --autocrop; the channels are measured on the GPU\n"
             "    -h, --help\n\nOPTIONS:\n"
             "    -a, --amplitude <amplitude>        Output amplitude [default: 1]\n"
             "    -b, --buffer <buffer-dur>          The maximum amount of audio to process ahead of time [default: 1]\n"
@@ -1083,6 +1106,9 @@ void usage() {
             "                                       crops a recording, in front of -s/-d; the peaks are measured on the GPU\n"
             "        --autocrop-window <dur>        The analysis window of --autocrop [default: 0.1]\n"
             "        --autocrop-percentile <p>      The noise-floor percentile of --autocrop, 0 ... 99 [default: 30]\n"
+            "        --channel-map <a,b,...>        With --frames-on-gpu: channel c of the job reads channel <c-th entry> of the\n"
+            "                                       input, one entry per channel of the file (a permutation or a copy; the\n"
+            "                                       rotation of --rotate-channels is 1,0 for stereo); applied on the GPU\n"
             "        --normalize <peak>             With --frames-on-gpu: measure the peak of the whole output on the GPU and scale\n"
             "                                       it to <peak> (1 = full scale) in front of the quantiser, any --output-format;\n"
             "                                       peak and gain are reported\n"
@@ -1180,6 +1206,22 @@ int run(int argc, char **argv) {
         else if (a == "--frames-on-gpu") o.frames_on_gpu = true;
         else if (a == "--fade-output") o.fade_output = true;
         else if (a == "--autocrop") o.autocrop = true;
+        else if (a == "--split-mono") o.split_mono = true;
+        else if (a == "--channel-map") {
+            const std::string v = need(i);
+            std::vector<uint32_t> m;
+            for (size_t b = 0; b <= v.size();) {
+                const size_t c = std::min(v.find(',', b), v.size());
+                const std::string t = v.substr(b, c - b);
+                char *end = nullptr;
+                const unsigned long long x = strtoull(t.c_str(), &end, 10);
+                if (t.empty() || *end || !isdigit((unsigned char)t[0]) || x > 65535)
+                    throw std::runtime_error("--channel-map takes a list of channel indices a,b,..., not " + v);
+                m.push_back((uint32_t)x);
+                b = c + 1;
+            }
+            o.channel_map = std::move(m);
+        }
         else if (a == "--autocrop-window") {
             o.autocrop_window_ms = dur(need(i));
             if (o.autocrop_window_ms == 0) throw std::runtime_error("--autocrop-window takes a duration above 0");
@@ -1252,6 +1294,10 @@ int run(int argc, char **argv) {
     if (o.fade_output && !o.frames_on_gpu) throw std::runtime_error("--fade-output needs --frames-on-gpu");
     // (the bins are measured by the engine on the raw frame block: the host reader has decoded it by then)
     if (o.autocrop && !o.frames_on_gpu) throw std::runtime_error("--autocrop needs --frames-on-gpu");
+    // (the map is an index in the engine's unpack kernel; the host path has --rotate-channels)
+    if (o.channel_map && !o.frames_on_gpu) throw std::runtime_error("--channel-map needs --frames-on-gpu");
+    // (the channels are measured by the engine on the raw frame block, and the copy is the engine's channel map)
+    if (o.split_mono && !o.frames_on_gpu) throw std::runtime_error("--split-mono needs --frames-on-gpu");
     if (o.frames_on_gpu) {
         // one engine call computes the whole job: nothing polls a watched kernel between windows, and the frame block is
         // neither sharded nor reordered
@@ -1293,7 +1339,18 @@ int run(int argc, char **argv) {
         raw_count = endp - first;
     };
     if (o.frames_on_gpu) {
-        raw = read_wav_raw(f);
+        // --channel-map: one index per channel of the file, each a channel of the file - checked once the header is read,
+        // before the data chunk, its page-locked memory and any engine work
+        raw = read_wav_raw(f, [&](const AudioSpec &s) {
+            if (!o.channel_map) return;
+            if (o.channel_map->size() != s.channels)
+                throw UsageError("--channel-map has " + std::to_string(o.channel_map->size()) + " entries, the input has " +
+                                 std::to_string(s.channels) + " channels");
+            for (const uint32_t m : *o.channel_map)
+                if (m >= s.channels)
+                    throw UsageError("--channel-map names channel " + std::to_string(m) + ", the input has channels 0 ... " +
+                                     std::to_string(s.channels - 1));
+        });
         raw_count = raw.frames;
         if (!o.autocrop) clip_raw();  // (with --autocrop: behind the crop, which needs the engine)
     } else {
@@ -1366,6 +1423,28 @@ int run(int argc, char **argv) {
         Engine eng;
         if (rc_engine_create(&cfg, &eng.h) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
         lap("engine create");
+        if (o.split_mono || o.channel_map) {
+            // recorder::auto_split_mono on the whole file (src/recorder.rs:64-70: in front of the autocrop), then
+            // Audio::rotate_channels' place behind -s / -d (src/main.rs:179-185): neither moves a sample. Row c of the job
+            // reads channel total[c] = split[user[c]] of the file: the user's map on the split audio.
+            if (!frames_api().set_map) throw std::runtime_error("--channel-map / --split-mono: the engine library has no rc_engine_set_channel_map");
+            const uint32_t C = spec.channels;
+            std::vector<uint32_t> split(C), total(C);
+            for (uint32_t c = 0; c < C; ++c) split[c] = c;
+            if (o.split_mono) {
+                if (!frames_api().channel_peaks || !frames_api().split_map)
+                    throw std::runtime_error("--split-mono: the engine library has no rc_engine_frames_channel_peaks");
+                std::vector<float> peaks(C);
+                int found = 0;
+                if (frames_api().channel_peaks(eng.h, raw.data.p, raw.frames, raw.format, peaks.data(), C) != RC_OK ||
+                    frames_api().split_map(peaks.data(), C, split.data(), &found) != RC_OK)
+                    throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+                if (found) fprintf(stderr, "Detected mono input from non-mono device. Automatically splitting.\n");  // src/recorder.rs:131
+            }
+            for (uint32_t c = 0; c < C; ++c) total[c] = split[o.channel_map ? (*o.channel_map)[c] : c];
+            if (frames_api().set_map(eng.h, total.data(), C) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+            lap("channel map");
+        }
         if (o.autocrop) {
             // recorder::autocrop_audio on the whole file, then -s / -d inside what remains (src/main.rs:173-181): an offset
             // and a count into the data chunk, no copy. The crop points are frames; the reference's round trip through a
@@ -1561,6 +1640,9 @@ int main(int argc, char **argv) {
         const int rc = run(argc, argv);
         report_peak_rss();
         return rc;
+    } catch (const UsageError &e) {
+        fprintf(stderr, "error: %s\n", e.what());
+        return 2;
     } catch (const std::exception &e) {
         fprintf(stderr, "error: %s\n", e.what());
         return 1;

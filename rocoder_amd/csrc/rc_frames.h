@@ -142,6 +142,31 @@ struct FramesPowerParams {
     uint64_t n_bins;
 };
 
+// FramesUnpackParams with a channel map (rc_engine_set_channel_map): row c of planar is filled from channel map[c] of the
+// block, planar[c * stride + frame0 + i] = sample (frame0 + i, map[c]). `map` is a device table of `channels` words, each
+// below `channels` (the engine's setter sees to it; the kernels clamp an entry to channels - 1 rather than trust it). A
+// source channel may feed several rows, or none. Every row gets every frame exactly once; nothing of the block is written.
+struct FramesUnpackMapParams {
+    FramesUnpackParams unpack;
+    const uint32_t *map;
+};
+
+// The peak of every channel of a block of raw frames (rc_engine_frames_channel_peaks; the definition is stated in
+// include/rocoder_hip.h). The block is what FramesUnpackParams describes, with the same licence to load whole 16-byte
+// groups around a range. The launch covers the job's frames [frame0, frame0 + n_frames) and adds to every channel:
+//   chan_bits[c] = max(chan_bits[c], bits of |x| with the sign bit cleared) over the range's samples of channel c, in the
+//   unsigned order of the bits: a NaN wins over +inf, +inf over every finite magnitude; x the reader's float of the sample.
+// Workgroups and launches join a channel with atomicMax, one per channel per workgroup that saw a non-zero sample.
+// chan_bits holds `channels` words, zeroed by the host in front of a job's first launch.
+struct FramesChannelPeaksParams {
+    const uint32_t *raw;
+    uint64_t raw_dwords;
+    uint32_t phase;  // 0 ... 3
+    uint32_t channels;
+    uint64_t frame0, n_frames;
+    uint32_t *chan_bits;
+};
+
 // (all: nothing is launched for n_frames == 0; a job of more than 2^27 frames goes out as several launches)
 hipError_t launch_frames_unpack(uint32_t format, const FramesUnpackParams &p, hipStream_t s);
 hipError_t launch_frames_pack(const FramesPackParams &p, hipStream_t s);
@@ -150,5 +175,7 @@ hipError_t launch_frames_peak(const FramesPeakParams &p, hipStream_t s);
 hipError_t launch_frames_pack_pcm_gain(uint32_t format, const FramesPackPcmGainParams &p, hipStream_t s);
 hipError_t launch_frames_fade(const FramesFadeParams &p, hipStream_t s);  // (nothing is launched for t1 <= t0)
 hipError_t launch_frames_power(uint32_t format, const FramesPowerParams &p, hipStream_t s);
+hipError_t launch_frames_unpack_map(uint32_t format, const FramesUnpackMapParams &p, hipStream_t s);
+hipError_t launch_frames_channel_peaks(uint32_t format, const FramesChannelPeaksParams &p, hipStream_t s);
 
 }  // namespace rc

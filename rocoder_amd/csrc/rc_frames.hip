@@ -533,6 +533,182 @@ __global__ __launch_bounds__(kFramesThreads) void frames_power_kernel(FramesPowe
         if (bins[i]) atomicMax(&p.bin_bits[bin_a + i], power_bits<FMT>(bins[i]));
 }
 
+// ---- the unpack kernels with a channel map (rc_engine_set_channel_map; FramesUnpackMapParams) ------------------------------
+// Row c is filled from channel map[c]. The global side is what it is without a map: whole tiles, consecutive lanes on
+// consecutive dwords. Up to kNarrowChannels channels the tile holds whole frames, and the map is an index in the LDS read.
+template <uint32_t FMT>
+__global__ __launch_bounds__(kFramesThreads) void frames_unpack_map_kernel(FramesUnpackMapParams pm) {
+    constexpr uint32_t B = fmt_bytes<FMT>();
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kNarrowLdsDwords];
+    const FramesUnpackParams &p = pm.unpack;
+    const uint32_t C = p.channels, tid = threadIdx.x;
+    const uint64_t f0 = p.frame0 + (uint64_t)blockIdx.x * kNarrowFrames, f_end = p.frame0 + p.n_frames;
+    if (f0 >= f_end) return;
+    const uint32_t tf = (uint32_t)(f_end - f0 < kNarrowFrames ? f_end - f0 : kNarrowFrames);
+    const uint64_t b0 = p.phase + f0 * C * B, b1 = b0 + (uint64_t)tf * C * B;
+    const uint64_t g0 = b0 >> 4, g1 = (b1 + 15) >> 4;  // 16-byte groups [g0, g1): at most 2050
+    const uint4 *raw4 = (const uint4 *)p.raw;
+    const uint64_t raw_groups = p.raw_dwords >> 2;
+    for (uint32_t g = tid; g < (uint32_t)(g1 - g0); g += kFramesThreads) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (g0 + g < raw_groups) v = raw4[g0 + g];
+        ((uint4 *)lds)[g] = v;
+    }
+    __syncthreads();
+    const uint32_t lead = (uint32_t)(b0 - (g0 << 4));  // bytes of the first group in front of the tile
+    for (uint32_t c = 0; c < C; ++c) {
+        const uint32_t m = min(pm.map[c], C - 1u);
+        float *row = p.planar + (uint64_t)c * p.stride + f0;
+        for (uint32_t fl = tid; fl < tf; fl += kFramesThreads)
+            row[fl] = pcm_decode<FMT>(lds_bits(lds, lead + (fl * C + m) * B));
+    }
+}
+
+// Above, a workgroup owns 64 frames of 64 ROWS (blockIdx.y: the row tile) and fetches, one after the other and each once,
+// the 64-channel SOURCE tiles that hold a channel one of its rows reads, in rising order: the load of a source tile is the
+// unmapped kernel's, and behind it the rows whose source lies in that tile are written, a wave per row. An identity-like
+// map costs one source tile per row tile, as without a map; a map that scatters the 64 rows of a tile over 64 source
+// tiles reads 64 tiles for it, every load still coalesced.
+template <uint32_t FMT>
+__global__ __launch_bounds__(kFramesThreads) void frames_unpack_map_wide_kernel(FramesUnpackMapParams pm) {
+    constexpr uint32_t B = fmt_bytes<FMT>();
+    __shared__ uint32_t lds[kWideFrames * kWidePitch];
+    __shared__ uint32_t src[kWideChannels];
+    const FramesUnpackParams &p = pm.unpack;
+    const uint32_t C = p.channels, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t f0 = p.frame0 + (uint64_t)blockIdx.x * kWideFrames, f_end = p.frame0 + p.n_frames;
+    const uint32_t c0 = blockIdx.y * kWideChannels;
+    if (f0 >= f_end || c0 >= C) return;
+    const uint32_t tf = (uint32_t)(f_end - f0 < kWideFrames ? f_end - f0 : kWideFrames);
+    const uint32_t tc = C - c0 < kWideChannels ? C - c0 : kWideChannels;
+    if (threadIdx.x < tc) src[threadIdx.x] = min(pm.map[c0 + threadIdx.x], C - 1u);
+    __syncthreads();
+    for (uint32_t next = 0;;) {
+        // the lowest source tile from `next` on that a row of this workgroup reads (every lane finds the same)
+        uint32_t t = UINT32_MAX;
+        for (uint32_t c = 0; c < tc; ++c) {
+            const uint32_t tc_of = src[c] / kWideChannels;
+            if (tc_of >= next && tc_of < t) t = tc_of;
+        }
+        if (t == UINT32_MAX) break;
+        const uint32_t s0 = t * kWideChannels, sc = C - s0 < kWideChannels ? C - s0 : kWideChannels;
+        for (uint32_t r = wave; r < tf; r += kWaves) {
+            const uint64_t s = p.phase + ((f0 + r) * C + s0) * B, d0 = s >> 2, d1 = (s + (uint64_t)sc * B + 3) >> 2;
+            const uint32_t nd = (uint32_t)(d1 - d0);  // at most 65
+            for (uint32_t j = lane; j < nd; j += 64) lds[r * kWidePitch + j] = d0 + j < p.raw_dwords ? p.raw[d0 + j] : 0u;
+        }
+        __syncthreads();
+        if (lane < tf) {
+            const uint32_t lead = (uint32_t)((p.phase + ((f0 + lane) * C + s0) * B) & 3u);
+            const uint32_t *row = lds + lane * kWidePitch;
+            for (uint32_t c = wave; c < tc; c += kWaves) {
+                const uint32_t m = src[c];
+                if (m / kWideChannels == t)
+                    p.planar[(uint64_t)(c0 + c) * p.stride + f0 + lane] = pcm_decode<FMT>(lds_bits(row, lead + (m - s0) * B));
+            }
+        }
+        next = t + 1;
+        __syncthreads();  // (the next source tile goes into the same LDS)
+    }
+}
+
+// ---- the peak of every channel of a raw frame block (rc_engine_frames_channel_peaks; FramesChannelPeaksParams) ------------
+// frames_power_kernel's integer key, with NaN kept: the bits of |x| for f32 as they are (a NaN sorts above +inf, +inf
+// above every finite magnitude), the magnitude of the integer otherwise; power_bits forms the float once per partial
+// result. A workgroup walks several tiles of the unpack kernels' shapes and joins each channel with one atomicMax.
+//   channels <= 8  kChanPeakNarrowTiles tiles of 1024 whole frames: a thread keeps one running maximum per channel in
+//                  registers over its frames; they are reduced across the wave, then across the waves through LDS
+//   channels  > 8  kChanPeakWideTiles tiles of 64 frames x 64 channels: a lane owns a channel of the tile (consecutive lanes
+//                  read consecutive samples of an LDS row), a wave every fourth frame
+constexpr uint32_t kChanPeakNarrowTiles = 4, kChanPeakWideTiles = 16;
+
+template <uint32_t FMT>
+__device__ __forceinline__ uint32_t chan_key(uint32_t v) {
+    if (FMT == PCM_F32) return v & 0x7fffffffu;
+    return power_key<FMT>(v);
+}
+
+template <uint32_t FMT>
+__global__ __launch_bounds__(kFramesThreads) void frames_channel_peaks_kernel(FramesChannelPeaksParams p) {
+    constexpr uint32_t B = fmt_bytes<FMT>();
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kNarrowLdsDwords];
+    __shared__ uint32_t wave_max[kNarrowChannels][kWaves];
+    const uint32_t C = p.channels, tid = threadIdx.x;
+    const uint64_t f_end = p.frame0 + p.n_frames;
+    uint64_t f0 = p.frame0 + (uint64_t)blockIdx.x * (kChanPeakNarrowTiles * kNarrowFrames);
+    if (f0 >= f_end) return;  // (the whole workgroup)
+    const uint4 *raw4 = (const uint4 *)p.raw;
+    const uint64_t raw_groups = p.raw_dwords >> 2;
+    uint32_t m[kNarrowChannels];
+#pragma unroll
+    for (uint32_t c = 0; c < kNarrowChannels; ++c) m[c] = 0;
+    for (uint32_t t = 0; t < kChanPeakNarrowTiles && f0 < f_end; ++t, f0 += kNarrowFrames) {
+        const uint32_t tf = (uint32_t)(f_end - f0 < kNarrowFrames ? f_end - f0 : kNarrowFrames);
+        const uint64_t b0 = p.phase + f0 * C * B, b1 = b0 + (uint64_t)tf * C * B;
+        const uint64_t g0 = b0 >> 4, g1 = (b1 + 15) >> 4;  // 16-byte groups [g0, g1): at most 2050
+        if (t) __syncthreads();  // (the tile before has been read)
+        for (uint32_t g = tid; g < (uint32_t)(g1 - g0); g += kFramesThreads) {
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (g0 + g < raw_groups) v = raw4[g0 + g];
+            ((uint4 *)lds)[g] = v;
+        }
+        __syncthreads();
+        const uint32_t lead = (uint32_t)(b0 - (g0 << 4));
+        for (uint32_t fl = tid; fl < tf; fl += kFramesThreads) {
+#pragma unroll
+            for (uint32_t c = 0; c < kNarrowChannels; ++c)
+                if (c < C) m[c] = max(m[c], chan_key<FMT>(lds_bits(lds, lead + (fl * C + c) * B)));
+        }
+    }
+#pragma unroll
+    for (uint32_t c = 0; c < kNarrowChannels; ++c) {
+        uint32_t v = m[c];
+        for (uint32_t off = 32; off; off >>= 1) v = max(v, (uint32_t)__shfl_down(v, off));
+        if ((tid & 63u) == 0) wave_max[c][tid >> 6] = v;
+    }
+    __syncthreads();
+    if (tid < C) {
+        uint32_t v = 0;
+        for (uint32_t w = 0; w < kWaves; ++w) v = max(v, wave_max[tid][w]);
+        if (v) atomicMax(&p.chan_bits[tid], power_bits<FMT>(v));
+    }
+}
+
+template <uint32_t FMT>
+__global__ __launch_bounds__(kFramesThreads) void frames_channel_peaks_wide_kernel(FramesChannelPeaksParams p) {
+    constexpr uint32_t B = fmt_bytes<FMT>();
+    __shared__ uint32_t lds[kWideFrames * kWidePitch];
+    __shared__ uint32_t wave_max[kWaves][kWideChannels];
+    const uint32_t C = p.channels, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t f_end = p.frame0 + p.n_frames;
+    uint64_t f0 = p.frame0 + (uint64_t)blockIdx.x * (kChanPeakWideTiles * kWideFrames);
+    const uint32_t c0 = blockIdx.y * kWideChannels;
+    if (f0 >= f_end || c0 >= C) return;  // (the whole workgroup)
+    const uint32_t tc = C - c0 < kWideChannels ? C - c0 : kWideChannels;
+    uint32_t m = 0;
+    for (uint32_t t = 0; t < kChanPeakWideTiles && f0 < f_end; ++t, f0 += kWideFrames) {
+        const uint32_t tf = (uint32_t)(f_end - f0 < kWideFrames ? f_end - f0 : kWideFrames);
+        if (t) __syncthreads();  // (the tile before has been read)
+        for (uint32_t r = wave; r < tf; r += kWaves) {
+            const uint64_t s = p.phase + ((f0 + r) * C + c0) * B, d0 = s >> 2, d1 = (s + (uint64_t)tc * B + 3) >> 2;
+            const uint32_t nd = (uint32_t)(d1 - d0);  // at most 65
+            for (uint32_t j = lane; j < nd; j += 64) lds[r * kWidePitch + j] = d0 + j < p.raw_dwords ? p.raw[d0 + j] : 0u;
+        }
+        __syncthreads();
+        if (lane < tc)
+            for (uint32_t r = wave; r < tf; r += kWaves) {
+                const uint32_t lead = (uint32_t)((p.phase + ((f0 + r) * C + c0) * B) & 3u);
+                m = max(m, chan_key<FMT>(lds_bits(lds + r * kWidePitch, lead + lane * B)));
+            }
+    }
+    wave_max[wave][lane] = m;
+    __syncthreads();
+    if (wave == 0 && lane < tc) {
+        for (uint32_t w = 1; w < kWaves; ++w) m = max(m, wave_max[w][lane]);
+        if (m) atomicMax(&p.chan_bits[c0 + lane], power_bits<FMT>(m));
+    }
+}
+
 constexpr uint64_t kMaxFramesPerLaunch = (uint64_t)1 << 27;  // (a grid dimension times the block stays far below 2^32)
 
 // the launches after the first of a job of more than kMaxFramesPerLaunch frames: the gain is stored once
@@ -602,6 +778,49 @@ hipError_t power_fmt(const FramesPowerParams &p, hipStream_t s) {
         q.n_frames = p.n_frames - done < per ? p.n_frames - done : per;
         const uint32_t tiles = (uint32_t)((q.n_frames * p.channels + TS - 1) / TS);
         frames_power_kernel<FMT><<<dim3(tiles), dim3(kFramesThreads), 0, s>>>(q);
+        const hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
+template <uint32_t FMT>
+hipError_t unpack_map_fmt(const FramesUnpackMapParams &pm, hipStream_t s) {
+    const FramesUnpackParams &p = pm.unpack;
+    const bool narrow = p.channels <= kNarrowChannels;
+    const uint32_t per = narrow ? kNarrowFrames : kWideFrames;
+    for (uint64_t done = 0; done < p.n_frames; done += kMaxFramesPerLaunch) {
+        FramesUnpackMapParams q = pm;
+        q.unpack.frame0 = p.frame0 + done;
+        q.unpack.n_frames = p.n_frames - done < kMaxFramesPerLaunch ? p.n_frames - done : kMaxFramesPerLaunch;
+        const uint32_t tiles = (uint32_t)((q.unpack.n_frames + per - 1) / per);
+        if (narrow) {
+            frames_unpack_map_kernel<FMT><<<dim3(tiles), dim3(kFramesThreads), 0, s>>>(q);
+        } else {
+            const uint32_t ct = (p.channels + kWideChannels - 1) / kWideChannels;
+            frames_unpack_map_wide_kernel<FMT><<<dim3(tiles, ct), dim3(kFramesThreads), 0, s>>>(q);
+        }
+        const hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
+template <uint32_t FMT>
+hipError_t channel_peaks_fmt(const FramesChannelPeaksParams &p, hipStream_t s) {
+    const bool narrow = p.channels <= kNarrowChannels;
+    const uint32_t per = narrow ? kChanPeakNarrowTiles * kNarrowFrames : kChanPeakWideTiles * kWideFrames;
+    for (uint64_t done = 0; done < p.n_frames; done += kMaxFramesPerLaunch) {
+        FramesChannelPeaksParams q = p;
+        q.frame0 = p.frame0 + done;
+        q.n_frames = p.n_frames - done < kMaxFramesPerLaunch ? p.n_frames - done : kMaxFramesPerLaunch;
+        const uint32_t groups = (uint32_t)((q.n_frames + per - 1) / per);
+        if (narrow) {
+            frames_channel_peaks_kernel<FMT><<<dim3(groups), dim3(kFramesThreads), 0, s>>>(q);
+        } else {
+            const uint32_t ct = (p.channels + kWideChannels - 1) / kWideChannels;
+            frames_channel_peaks_wide_kernel<FMT><<<dim3(groups, ct), dim3(kFramesThreads), 0, s>>>(q);
+        }
         const hipError_t err = hipGetLastError();
         if (err != hipSuccess) return err;
     }
@@ -727,6 +946,38 @@ hipError_t launch_frames_power(uint32_t format, const FramesPowerParams &pp, hip
     case PCM_I24: return power_fmt<PCM_I24>(p, s);
     case PCM_I32: return power_fmt<PCM_I32>(p, s);
     default: return power_fmt<PCM_F32>(p, s);
+    }
+}
+
+hipError_t launch_frames_unpack_map(uint32_t format, const FramesUnpackMapParams &pm, hipStream_t s) {
+    const FramesUnpackParams &p = pm.unpack;
+    if (p.n_frames == 0) return hipSuccess;
+    if (p.channels == 0 || p.channels > 65535u || p.phase > 3u || (p.raw_dwords & 3u) || ((uintptr_t)p.raw & 15u) || !pm.map)
+        return hipErrorInvalidValue;
+    switch (format) {
+    case PCM_U8: return unpack_map_fmt<PCM_U8>(pm, s);
+    case PCM_I16: return unpack_map_fmt<PCM_I16>(pm, s);
+    case PCM_I24: return unpack_map_fmt<PCM_I24>(pm, s);
+    case PCM_I32: return unpack_map_fmt<PCM_I32>(pm, s);
+    case PCM_F32: return unpack_map_fmt<PCM_F32>(pm, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_frames_channel_peaks(uint32_t format, const FramesChannelPeaksParams &p, hipStream_t s) {
+    if (!pcm_bytes(format)) return hipErrorInvalidValue;
+    if (p.n_frames == 0) return hipSuccess;
+    if (p.channels == 0 || p.channels > 65535u || p.phase > 3u || (p.raw_dwords & 3u) || ((uintptr_t)p.raw & 15u) || !p.chan_bits ||
+        p.frame0 + p.n_frames < p.frame0)
+        return hipErrorInvalidValue;
+    // the range's last byte lies inside raw
+    if ((p.phase + (p.frame0 + p.n_frames) * p.channels * pcm_bytes(format) + 3) / 4 > p.raw_dwords) return hipErrorInvalidValue;
+    switch (format) {
+    case PCM_U8: return channel_peaks_fmt<PCM_U8>(p, s);
+    case PCM_I16: return channel_peaks_fmt<PCM_I16>(p, s);
+    case PCM_I24: return channel_peaks_fmt<PCM_I24>(p, s);
+    case PCM_I32: return channel_peaks_fmt<PCM_I32>(p, s);
+    default: return channel_peaks_fmt<PCM_F32>(p, s);
     }
 }
 

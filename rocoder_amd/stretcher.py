@@ -229,6 +229,19 @@ def autocrop_points(bin_peak, bin_frames: int, n_frames: int, percentile: int = 
     return (int(start.value), int(end.value)) if found.value else None
 
 
+def split_mono_map(chan_peak):
+    """The reference's auto_split_mono decision (src/recorder.rs:118-144) from the peaks `Engine.frames_channel_peaks`
+    gives: (map, found). Where all channels but one are silent (peak == 0; a NaN peak is not silent), `map` sends every row
+    to that channel and `found` is True - one live channel alone included, where the map is the identity; otherwise the
+    identity map and False. `map` is what `Engine.set_channel_map` takes. Pure host code (rc_split_mono_map)."""
+    peaks = np.ascontiguousarray(chan_peak, np.float32).reshape(-1)
+    out = np.zeros(max(peaks.size, 1), np.uint32)
+    found = C.c_int(0)
+    L = _lib.lib()
+    check(L.rc_split_mono_map(_fp(peaks), peaks.size, out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(found)), L)
+    return [int(v) for v in out[:peaks.size]], bool(found.value)
+
+
 class _ViewOwner:
     """`base` of the arrays next_window_view hands out: keeps the engine alive and knows whether it is still current."""
 
@@ -497,6 +510,18 @@ class Engine:
         assert got.value == n_bins
         return out[:n_bins]
 
+    def frames_channel_peaks(self, frames, fmt: Optional[str] = None) -> np.ndarray:
+        """The peak of every channel of a block of interleaved PCM frames, measured on the GPU on the raw block
+        (rc_engine_frames_channel_peaks): float32 [channels], the float whose bits are the largest bits of |x| over the
+        channel's samples - a NaN sample wins, then +-inf, then the largest finite magnitude; exactly 0 where the
+        reference's all-zero test (src/recorder.rs:122) holds. `frames` and `fmt` are `stretch_frames`'s. The input of
+        `split_mono_map`. The engine's fade, channel map, kernels and streaming state are left as they were."""
+        raw, code, n = self._raw_frames(frames, fmt)
+        out = np.empty(self.channels, np.float32)
+        src = C.c_void_p(raw.ctypes.data if raw.size else out.ctypes.data)  # (no frames: any non-null pointer)
+        self._check(self._L.rc_engine_frames_channel_peaks(self._h, src, n, code, _fp(out), self.channels))
+        return out
+
     def stretch_device_ptr(self, d_in: int, in_stride: int, in_len: int, d_out: int, out_stride: int,
                            out_cap: int, stream: int = 0) -> int:
         got = C.c_size_t(0)
@@ -574,6 +599,22 @@ class Engine:
     def set_device_kernel_source(self, src, name: Optional[str] = None):
         """compile_device_kernel + load_device_kernel."""
         self.load_device_kernel(compile_device_kernel(src, name))
+
+    def set_channel_map(self, channel_map: Optional[Sequence[int]] = None):
+        """Row c of every `stretch_frames` call from now on reads channel `channel_map[c]` of the frame block
+        (rc_engine_set_channel_map): one index below `channels` per channel; a source channel may feed several rows, or
+        none. The result is what the call gives with no map on the block `frames[:, channel_map]`. None (or an empty
+        list) clears the map. `stretch_host`, `frames_power`, `frames_channel_peaks`, the device and streaming calls
+        are untouched. A list of the wrong length or with an index out of range raises (RC_EINVAL) and the previous map
+        stays."""
+        if channel_map is None or len(channel_map) == 0:
+            self._check(self._L.rc_engine_set_channel_map(self._h, None, 0))
+            return
+        vals = [int(v) for v in channel_map]
+        if any(not 0 <= v < 2 ** 32 for v in vals):
+            raise ValueError("channel indices are unsigned 32-bit integers")
+        arr = (C.c_uint32 * len(vals))(*vals)
+        self._check(self._L.rc_engine_set_channel_map(self._h, arr, len(vals)))
 
     def set_output_fade(self, fade_in: int = 0, fade_out_start: Optional[int] = None, fade_out_len: int = 0):
         """The reference's sqrt fade-in over the first `fade_in` output frames and fade-out over `fade_out_len` frames
