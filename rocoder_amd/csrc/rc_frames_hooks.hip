@@ -1,0 +1,56 @@
+// Test-hook entries for the launchers of rc_frames.h: compiled into librocoder_hip_hooks.so only (`make hooks`), never
+// into the product library. One wrapper per launcher: the fields of its parameter block as plain scalars and device
+// pointers, a launch on the null stream, a synchronise, the hipError_t as an int. No logic, no clamping, no defaults and
+// no allocation: what a launcher does with a set of arguments is what the test sees (tests/frameskernelutil.py sizes
+// every buffer and asserts the sizes before a call).
+#include "rc_frames.h"
+
+namespace {
+int finish(hipError_t err) { return (int)(err != hipSuccess ? err : hipStreamSynchronize(nullptr)); }
+}  // namespace
+
+extern "C" {
+
+int rc_test_frames_unpack(uint32_t format, const uint32_t *raw, uint64_t raw_dwords, uint32_t phase, uint32_t channels,
+                          uint64_t frame0, uint64_t n_frames, float *planar, uint64_t stride) {
+    return finish(rc::launch_frames_unpack(format, rc::FramesUnpackParams{raw, raw_dwords, phase, channels, frame0, n_frames, planar, stride},
+                                           nullptr));
+}
+
+int rc_test_frames_unpack_map(uint32_t format, const uint32_t *raw, uint64_t raw_dwords, uint32_t phase, uint32_t channels,
+                              uint64_t frame0, uint64_t n_frames, float *planar, uint64_t stride, const uint32_t *map) {
+    return finish(rc::launch_frames_unpack_map(
+        format, rc::FramesUnpackMapParams{rc::FramesUnpackParams{raw, raw_dwords, phase, channels, frame0, n_frames, planar, stride}, map},
+        nullptr));
+}
+
+int rc_test_frames_pack(const float *planar, uint64_t stride, float *frames, uint64_t n_frames, uint32_t channels) {
+    return finish(rc::launch_frames_pack(rc::FramesPackParams{planar, stride, frames, n_frames, channels}, nullptr));
+}
+
+int rc_test_frames_pack_pcm(uint32_t format, const float *planar, uint64_t stride, unsigned char *target, uint32_t phase,
+                            uint32_t channels, uint64_t n_frames, uint64_t *clipped) {
+    return finish(rc::launch_frames_pack_pcm(format, rc::FramesPackPcmParams{planar, stride, target, phase, channels, n_frames, clipped},
+                                             nullptr));
+}
+
+int rc_test_frames_pack_pcm_gain(uint32_t format, const float *planar, uint64_t stride, unsigned char *target, uint32_t phase,
+                                 uint32_t channels, uint64_t n_frames, uint64_t *clipped, rc::FramesNormWords *norm,
+                                 float target_peak, uint32_t store_gain) {
+    return finish(rc::launch_frames_pack_pcm_gain(
+        format,
+        rc::FramesPackPcmGainParams{rc::FramesPackPcmParams{planar, stride, target, phase, channels, n_frames, clipped}, norm, target_peak,
+                                    store_gain},
+        nullptr));
+}
+
+int rc_test_frames_peak(const float *planar, uint64_t stride, uint64_t n_frames, uint32_t channels, rc::FramesNormWords *norm) {
+    return finish(rc::launch_frames_peak(rc::FramesPeakParams{planar, stride, n_frames, channels, norm}, nullptr));
+}
+
+int rc_test_frames_fade(float *planar, uint64_t stride, uint32_t channels, uint64_t in_len, uint64_t out_start, uint64_t out_len,
+                        uint64_t t0, uint64_t t1) {
+    return finish(rc::launch_frames_fade(rc::FramesFadeParams{planar, stride, channels, in_len, out_start, out_len, t0, t1}, nullptr));
+}
+
+}  // extern "C"

@@ -35,8 +35,14 @@ def test_library_loads_and_exports_every_declared_symbol():
 def test_product_library_reads_no_diagnostic_variable_and_hook_build_loads():
     """ROCODER_DIAG and the run-planner tuning variables change what an engine computes with; only the test-hook
     build (`make hooks`, -DRC_TEST_HOOKS=1) may read them - the product library must not even contain their names.
-    The hook build exports the same C-ABI."""
+    The hook build exports the same C-ABI. The entries that hand the launchers of rc_frames.h to the tests
+    (rc_test_frames_*, rc_frames_hooks.hip) are in the hook build alone as well."""
+    frames_hooks = ["rc_test_frames_unpack", "rc_test_frames_unpack_map", "rc_test_frames_pack", "rc_test_frames_pack_pcm",
+                    "rc_test_frames_pack_pcm_gain", "rc_test_frames_peak", "rc_test_frames_fade"]
     blob = open(_lib.LIB_PATH, "rb").read()
+    assert b"rc_test_frames_" not in blob
+    for n in frames_hooks:
+        assert not hasattr(_lib.lib(), n), n
     for name in (b"ROCODER_DIAG", b"ROCODER_ROUNDS", b"ROCODER_MIN_RUN", b"ROCODER_B4_ROUNDS"):
         assert name not in blob, name
     assert b"hop3_kernel" not in blob  # the previous kernel generation lives in the hook build only
@@ -44,7 +50,7 @@ def test_product_library_reads_no_diagnostic_variable_and_hook_build_loads():
     assert b"ROCODER_DIAG" in hooks and b"hop3_kernel" in hooks
     with _lib.hooks_library() as H:
         assert _lib.lib() is H
-        for n in _header_functions():
+        for n in _header_functions() + frames_hooks:
             assert hasattr(H, n), n
         assert H.rc_abi_version() == _lib.lib().rc_abi_version()
     assert _lib.lib() is not H
