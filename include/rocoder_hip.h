@@ -197,7 +197,8 @@ int rc_engine_stretch_frames(rc_engine *e, const void *frames, size_t n_frames, 
  *   RC_PCM_I32  S 2147483647  [-2^31, 2^31 - 1]      4 bytes ((float)S is 2^31; +1.0 gives 2^31 - 1, not INT_MIN)
  *   RC_PCM_F32  the bits unchanged: the output of rc_engine_stretch_frames
  * S is the divisor rc_engine_stretch_frames reads with, so decoding what this wrote and encoding it again gives the
- * same bytes for u8 / i16 / i24. There is no dither and no noise shaping. *clipped (may be NULL) receives the number of
+ * same bytes for u8 / i16 / i24. There is no dither unless rc_engine_set_output_dither has set one (below; with it that
+ * round trip no longer holds), and no noise shaping beyond that entry's first-order high-pass. *clipped (may be NULL) receives the number of
  * output samples with !(|x| <= 1) - beyond full scale, or NaN - whatever out_format is, RC_PCM_F32 included: the
  * stretch overshoots full scale regularly, and an integer format has to clip what a float file hides.
  * RC_EINVAL: a null pointer (other than clipped), format or out_format outside 1 ... 5; RC_ECAPACITY: out_cap_frames too
@@ -263,6 +264,36 @@ int rc_engine_stretch_frames_norm(rc_engine *e, const void *frames, size_t n_fra
  * not. Only the frames a fade changes are touched: fades of 1 s cost 2 s of samples, not the job. */
 #define RC_FADE_NONE UINT64_MAX
 int rc_engine_set_output_fade(rc_engine *e, uint64_t in_len, uint64_t out_start, uint64_t out_len);
+/* Dither in front of the integer quantiser of rc_engine_stretch_frames_pcm and rc_engine_stretch_frames_norm: without it
+ * a signal below half a quantiser step - the tail of a fade-out, a quiet passage in 8 or 16 bits - turns into
+ * signal-correlated distortion and then into digital silence; with it the quantisation error is noise that does not
+ * depend on the signal. The dither is engine state, set once, like the output fade and the channel map; RC_DITHER_NONE
+ * is the state after rc_engine_create. It is counter-based: a sample's dither depends on the seed, its channel and its
+ * output frame alone, so the bytes of a job do not depend on how the job is cut into chunks, launches or tiles.
+ * The definition, bit for bit, for output frame t (absolute, from 0) and job channel c (the row of the job: a channel
+ * map does not change it):
+ *   K(c)    rc_phase_key(seed, c, 0xFFFFFFFFFF): the hop index 2^40 - 1 is one that no job reaches, so the draws stay
+ *           apart from the phase source even under the same seed.
+ *   h(c, t) rc_phase_hash(K(c), (uint32_t)t): the counter is t mod 2^32, the sequence repeats after 2^32 frames.
+ *   RC_DITHER_TPDF     i = (int)(h >> 16) - (int)(h & 0xFFFF): triangular, 2 LSB peak to peak, white.
+ *   RC_DITHER_TPDF_HP  i = (int)(h(c, t) >> 16) - (int)(h(c, (uint32_t)(t - 1)) >> 16): the difference of consecutive
+ *                      uniform draws - the same triangle, high-passed (at t = 0 the earlier counter is 0xFFFFFFFF).
+ *   d       (float)i * 2^-16: both steps exact in f32, |d| < 1.
+ *   t1 = x * (float)S, ONE IEEE f32 multiplication;  t2 = t1 + d, ONE IEEE f32 addition, not contracted into an fma with
+ *   the multiplication;  r = rint(t2), ties to even, NaN -> 0, clamped to [LO, HI]; S, LO, HI as stated at
+ *   rc_engine_stretch_frames_pcm. Under rc_engine_stretch_frames_norm x is z = y * gain as stated there.
+ * *clipped counts !(|x| <= 1) on the value in front of the dither: the same number with and without it. Near i24 full
+ * scale t1 + d rounds to f32's half steps, and a code can differ from the undithered one by 2. Decoding what a dithered
+ * call wrote and encoding it again does not give the same bytes.
+ * Reach: out_format RC_PCM_U8, RC_PCM_I16 and RC_PCM_I24 of those two entries, under a host frequency kernel as well.
+ * RC_PCM_I32 and RC_PCM_F32 are written exactly as without dither (an f32 sample holds 24 significant bits: the i32
+ * quantiser adds no error that a step of noise could randomise). rc_engine_stretch_frames, rc_engine_stretch_host, the
+ * device forms, the streaming seam and rc_multi take no dither. With RC_DITHER_NONE every byte is what it is without
+ * this entry. RC_EINVAL: a null engine, mode > 2; the previous state stays. */
+#define RC_DITHER_NONE 0
+#define RC_DITHER_TPDF 1
+#define RC_DITHER_TPDF_HP 2
+int rc_engine_set_output_dither(rc_engine *e, uint32_t mode, uint64_t seed);
 /* The reference's autocrop (src/recorder.rs:146-191, applied to a recording in front of `-s/-d`, src/main.rs:173-181):
  * the peak of every bin of a block of frames, measured on the device on the raw block, and the crop points those peaks
  * give. Three entries; a caller cuts by pointer arithmetic - the frames entries above take frames at any byte alignment.

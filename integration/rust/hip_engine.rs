@@ -29,6 +29,9 @@ pub const RC_PCM_I16: u32 = 2;
 pub const RC_PCM_I24: u32 = 3;
 pub const RC_PCM_I32: u32 = 4;
 pub const RC_PCM_F32: u32 = 5;
+pub const RC_DITHER_NONE: u32 = 0;
+pub const RC_DITHER_TPDF: u32 = 1;
+pub const RC_DITHER_TPDF_HP: u32 = 2;
 
 /// `rc_config`: the arguments of `Stretcher::new` (src/stretcher.rs:30-39) for all channels of a job.
 #[repr(C)]
@@ -89,6 +92,8 @@ extern "C" {
                                          target_peak: f32, out_frames_len: *mut usize, peak: *mut f32,
                                          gain: *mut f32, clipped: *mut u64) -> c_int;
     pub fn rc_engine_set_output_fade(e: *mut RcEngine, in_len: u64, out_start: u64, out_len: u64) -> c_int;  // RC_FADE_NONE = u64::MAX
+    // dither in front of the u8 / i16 / i24 quantiser of the two entries above: RC_DITHER_*, counter-based on (seed, channel, frame)
+    pub fn rc_engine_set_output_dither(e: *mut RcEngine, mode: u32, seed: u64) -> c_int;
     // the reference's autocrop (src/recorder.rs:94-113,146-191): per-bin peaks of the raw block, then the crop points
     pub fn rc_frames_power_bins(n_frames: usize, bin_frames: u64) -> usize;
     pub fn rc_engine_frames_power(e: *mut RcEngine, frames: *const c_void, n_frames: usize, format: u32,

@@ -185,6 +185,7 @@ struct FramesApi {
     decltype(&rc_engine_stretch_frames_pcm) stretch_pcm = nullptr;  // (--output-format only: may be missing)
     decltype(&rc_engine_stretch_frames_norm) stretch_norm = nullptr;  // (--normalize only: may be missing)
     decltype(&rc_engine_set_output_fade) set_fade = nullptr;  // (--fade-output only: may be missing)
+    decltype(&rc_engine_set_output_dither) set_dither = nullptr;  // (--dither only: may be missing)
     decltype(&rc_engine_frames_power) power = nullptr;        // (--autocrop only: may be missing, both or neither)
     decltype(&rc_autocrop_points) crop_points = nullptr;
     decltype(&rc_engine_set_channel_map) set_map = nullptr;  // (--channel-map / --split-mono only: may be missing)
@@ -200,6 +201,7 @@ static const FramesApi &frames_api() {
         a.stretch_pcm = (decltype(a.stretch_pcm))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames_pcm");
         a.stretch_norm = (decltype(a.stretch_norm))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames_norm");
         a.set_fade = (decltype(a.set_fade))dlsym(RTLD_DEFAULT, "rc_engine_set_output_fade");
+        a.set_dither = (decltype(a.set_dither))dlsym(RTLD_DEFAULT, "rc_engine_set_output_dither");
         a.power = (decltype(a.power))dlsym(RTLD_DEFAULT, "rc_engine_frames_power");
         a.crop_points = (decltype(a.crop_points))dlsym(RTLD_DEFAULT, "rc_autocrop_points");
         a.set_map = (decltype(a.set_map))dlsym(RTLD_DEFAULT, "rc_engine_set_channel_map");
@@ -363,9 +365,11 @@ Audio read_wav(FILE *f, uint32_t *format = nullptr) {
 
 // --output-format: float -> PCM sample, the definition of include/rocoder_hip.h (rc_engine_stretch_frames_pcm) and, bit
 // for bit, what the engine's pack kernel computes: t = x * S is one IEEE multiplication (nothing to fuse it with),
-// rint rounds to nearest even (the default rounding mode), NaN gives 0, the result is clamped. No dither.
+// rint rounds to nearest even (the default rounding mode), NaN gives 0, the result is clamped. With `d` (--dither: u8,
+// i16 and i24 only) the dither is added to t in ONE f32 addition in front of rint, the definition of
+// rc_engine_set_output_dither.
 uint32_t pcm_sample_bytes(uint32_t fmt) { return fmt == RC_PCM_U8 ? 1u : fmt == RC_PCM_I16 ? 2u : fmt == RC_PCM_I24 ? 3u : 4u; }
-inline void pcm_encode(float x, uint32_t fmt, unsigned char *dst) {
+inline void pcm_encode(float x, uint32_t fmt, unsigned char *dst, const float *d = nullptr) {
     if (fmt == RC_PCM_F32) {
         memcpy(dst, &x, 4);
         return;
@@ -374,6 +378,7 @@ inline void pcm_encode(float x, uint32_t fmt, unsigned char *dst) {
     const double lo = fmt == RC_PCM_U8 ? -128.0 : fmt == RC_PCM_I16 ? -32768.0 : fmt == RC_PCM_I24 ? -8388608.0 : -2147483648.0;
     const double hi = fmt == RC_PCM_U8 ? 127.0 : fmt == RC_PCM_I16 ? 32767.0 : fmt == RC_PCM_I24 ? 8388607.0 : 2147483647.0;
     volatile float t = x * S;  // (volatile: rounded to f32 here, whatever the target's evaluation method)
+    if (d) t = t + *d;  // (and here: an addition of its own, never an fma with the line above)
     double r = std::rint((double)t);  // (t is an f32: its nearest integer is the same in double)
     if (std::isnan(r)) r = 0.0;
     r = std::min(std::max(r, lo), hi);
@@ -382,6 +387,32 @@ inline void pcm_encode(float x, uint32_t fmt, unsigned char *dst) {
     for (uint32_t b = 0; b < pcm_sample_bytes(fmt); ++b) dst[b] = (unsigned char)(u >> (8 * b));
 }
 inline bool pcm_clipped(float x) { return !(std::fabs(x) <= 1.0f); }  // beyond full scale, or NaN
+
+// --dither on the host path: the definition of include/rocoder_hip.h (rc_engine_set_output_dither) over the library's own
+// rc_phase_key and rc_phase_hash, so that the same flags give the same file with and without --frames-on-gpu. The writer
+// knows the absolute frame and the channel of every sample it encodes. The two entries are looked up when a dither asks
+// for them, as the frames entries above: without the flag the CLI runs over a library that lacks them.
+struct HostDither {
+    uint32_t mode = RC_DITHER_NONE;
+    std::vector<uint64_t> keys;  // K(c), one per channel
+    decltype(&rc_phase_hash) hash = nullptr;
+    HostDither() = default;
+    HostDither(uint32_t mode_, uint64_t seed, uint32_t channels) : mode(mode_) {
+        if (mode == RC_DITHER_NONE) return;
+        const auto key = (decltype(&rc_phase_key))dlsym(RTLD_DEFAULT, "rc_phase_key");
+        hash = (decltype(hash))dlsym(RTLD_DEFAULT, "rc_phase_hash");
+        if (!key || !hash) throw std::runtime_error("--dither: the engine library has no rc_phase_key / rc_phase_hash");
+        // the hop index 2^40 - 1 is one that no job reaches
+        for (uint32_t c = 0; c < channels; ++c) keys.push_back(key(seed, c, 0xFFFFFFFFFFull));
+    }
+    // on for this format: u8, i16, i24
+    bool on(uint32_t fmt) const { return mode != RC_DITHER_NONE && (fmt == RC_PCM_U8 || fmt == RC_PCM_I16 || fmt == RC_PCM_I24); }
+    float d(uint32_t c, uint64_t t) const {
+        const uint32_t h = hash(keys[c], (uint32_t)t);
+        const int i = mode == RC_DITHER_TPDF_HP ? (int)(h >> 16) - (int)(hash(keys[c], (uint32_t)(t - 1)) >> 16) : (int)(h >> 16) - (int)(h & 0xFFFFu);
+        return (float)i * (1.0f / 65536.0f);
+    }
+};
 
 // WAV as hound writes 32-bit float (audio_files.rs:68-81,203-226): WAVE_FORMAT_EXTENSIBLE header + interleaved frames.
 // The integer formats of --output-format get the same header with the PCM subformat and their own bits, block_align
@@ -415,21 +446,28 @@ bool write_wav_pad(FILE *f, const AudioSpec &spec, uint64_t frames, uint32_t fmt
     return !((frames * spec.channels * pcm_sample_bytes(fmt)) & 1) || fputc(0, f) == 0;
 }
 
-// interleave and encode k frames from chans[c] + i0 into `row` (k * channels * bytes); returns the clipped samples
-uint64_t encode_frames(const float *const *chans, uint32_t ch, size_t i0, size_t k, uint32_t fmt, unsigned char *row) {
+// interleave and encode k frames from chans[c] + i0 into `row` (k * channels * bytes); returns the clipped samples.
+// dith (may be null): the frame at i0 is absolute output frame t0.
+uint64_t encode_frames(const float *const *chans, uint32_t ch, size_t i0, size_t k, uint32_t fmt, unsigned char *row,
+                       const HostDither *dith = nullptr, uint64_t t0 = 0) {
     const uint32_t sb = pcm_sample_bytes(fmt);
+    const bool dithered = dith && dith->on(fmt);
     uint64_t clipped = 0;
     for (size_t i = 0; i < k; ++i)
         for (uint32_t c = 0; c < ch; ++c) {
             const float x = chans[c][i0 + i];
             clipped += pcm_clipped(x);
-            pcm_encode(x, fmt, row + (i * ch + c) * sb);
+            if (dithered) {
+                const float d = dith->d(c, t0 + i);
+                pcm_encode(x, fmt, row + (i * ch + c) * sb, &d);
+            } else
+                pcm_encode(x, fmt, row + (i * ch + c) * sb);
         }
     return clipped;
 }
 
 // (*clipped, where given, receives the count of samples beyond full scale)
-void write_wav(const std::string &path, const Audio &a, uint32_t fmt = RC_PCM_F32, uint64_t *clipped = nullptr) {
+void write_wav(const std::string &path, const Audio &a, uint32_t fmt = RC_PCM_F32, uint64_t *clipped = nullptr, const HostDither *dith = nullptr) {
     FILE *f = fopen(path.c_str(), "wb");
     if (!f) throw std::runtime_error("cannot create " + path);
     const uint32_t ch = a.spec.channels;
@@ -451,7 +489,7 @@ void write_wav(const std::string &path, const Audio &a, uint32_t fmt = RC_PCM_F3
         uint64_t n = 0;
         for (uint64_t i0 = 0; i0 < frames; i0 += 4096) {
             const uint64_t k = std::min<uint64_t>(4096, frames - i0);
-            n += encode_frames(chans.data(), ch, (size_t)i0, (size_t)k, fmt, row.data());
+            n += encode_frames(chans.data(), ch, (size_t)i0, (size_t)k, fmt, row.data(), dith, i0);
             fwrite(row.data(), sb, (size_t)(k * ch), f);
         }
         (void)write_wav_pad(f, a.spec, frames, fmt);
@@ -474,6 +512,7 @@ struct WavStreamWriter {
     uint32_t fmt = RC_PCM_F32;
     bool count = false;    // --output-format given: samples are encoded through pcm_encode and the clipped ones counted
     uint64_t clipped = 0;
+    HostDither dither;     // --dither: frame `frames` is the absolute output frame of the next sample appended
     // The samples go to "<path>.part" and the file takes its name in finish(): a run that fails half way (a device
     // error, a full disk) leaves no output file with empty size fields behind (the reference writes nothing before the
     // whole output exists, src/main.rs:197-203)
@@ -497,7 +536,7 @@ struct WavStreamWriter {
             enc.resize((size_t)ch * std::min<size_t>(n, 4096) * sb);
             for (size_t i0 = 0; i0 < n; i0 += 4096) {
                 const size_t k = std::min<size_t>(4096, n - i0);
-                clipped += encode_frames(chans.data(), ch, i0, k, fmt, enc.data());
+                clipped += encode_frames(chans.data(), ch, i0, k, fmt, enc.data(), &dither, frames + i0);
                 if (fwrite(enc.data(), sb, k * ch, f) != k * ch) throw std::runtime_error("write failed (disk full?)");
             }
             frames += n;
@@ -1075,6 +1114,11 @@ struct Opt {  // src/main.rs:27-122
     // recorder::auto_split_mono (src/recorder.rs:118-144, in front of the autocrop, :64-70): measured on the GPU (--frames-on-gpu)
     bool split_mono = false;
     std::optional<float> normalize;  // not in the reference: the output's peak is brought to this level on the GPU (--frames-on-gpu)
+    // not in the reference (it writes f32): dither in front of the u8 / i16 / i24 quantiser, on the GPU under --frames-on-gpu
+    // and in the writer otherwise - the same bytes
+    uint32_t dither = RC_DITHER_NONE;
+    bool dither_given = false;
+    std::optional<uint64_t> dither_seed;  // [default: --seed]
 };
 
 void usage() {
@@ -1102,6 +1146,11 @@ void usage() {
             "        --output-format <fmt>          Sample format of the output file: f32 | u8 | i16 | i24 | i32 | input (that of\n"
             "                                       the input file) [default: f32]. Integers are rounded to nearest and clipped;\n"
             "                                       the number of clipped samples is reported\n"
+            "        --dither <mode>                none | tpdf | tpdf-hp: dither in front of the quantiser of --output-format u8, i16\n"
+            "                                       or i24 (refused with any other format): triangular noise of 2 LSB peak to\n"
+            "                                       peak, white (tpdf) or high-passed (tpdf-hp); on the GPU with --frames-on-gpu,\n"
+            "                                       the same bytes without [default: none]\n"
+            "        --dither-seed <u64>            Seed of --dither [default: the value of --seed]\n"
             "        --autocrop                     With --frames-on-gpu: crop dead air off both ends of the input, as the reference\n"
             "                                       crops a recording, in front of -s/-d; the peaks are measured on the GPU\n"
             "        --autocrop-window <dur>        The analysis window of --autocrop [default: 0.1]\n"
@@ -1165,6 +1214,34 @@ int run(int argc, char **argv) {
             fwrite(y.data(), 1, y.size() - 1, g);
             fclose(g);
             printf("%zu %llu\n", x.size(), (unsigned long long)clipped);
+            return 0;
+        } else if (a == "--encode-pcm-dither") {  // test hook: frame-major f32 frames -> the bytes --output-format <fmt> --dither <mode> writes
+            const std::string name = need(i), mode = need(i), seed = need(i), chs = need(i), t0s = need(i), in = need(i), outp = need(i);
+            const uint32_t fmt = pcm_format_by_name(name);
+            const uint32_t md = mode == "none" ? RC_DITHER_NONE : mode == "tpdf" ? RC_DITHER_TPDF : mode == "tpdf-hp" ? RC_DITHER_TPDF_HP : 99u;
+            const uint32_t ch = (uint32_t)strtoul(chs.c_str(), nullptr, 10);
+            const uint64_t t0 = strtoull(t0s.c_str(), nullptr, 0);
+            if (!fmt || md == 99u || !ch) throw std::runtime_error("bad --encode-pcm-dither arguments");
+            FILE *f = fopen(in.c_str(), "rb");
+            if (!f) throw std::runtime_error("cannot open " + in);
+            std::vector<float> x;
+            float v;
+            while (fread(&v, 4, 1, f) == 1) x.push_back(v);
+            fclose(f);
+            const HostDither dith(md, strtoull(seed.c_str(), nullptr, 0), ch);
+            const uint32_t sb = pcm_sample_bytes(fmt);
+            std::vector<unsigned char> y(x.size() * sb + 1);
+            uint64_t clipped = 0;
+            for (size_t k = 0; k < x.size(); ++k) {
+                clipped += pcm_clipped(x[k]);
+                const float d = dith.on(fmt) ? dith.d((uint32_t)(k % ch), t0 + k / ch) : 0.0f;
+                pcm_encode(x[k], fmt, y.data() + k * sb, dith.on(fmt) ? &d : nullptr);
+            }
+            FILE *g = fopen(outp.c_str(), "wb");
+            if (!g) throw std::runtime_error("cannot create " + outp);
+            fwrite(y.data(), 1, y.size() - 1, g);
+            fclose(g);
+            printf("%zu %llu\n", x.size() / ch, (unsigned long long)clipped);
             return 0;
         } else if (a == "--encode-wav") {  // test hook: raw f32 planar [channels][frames] -> the WAV --output-format <fmt> writes
             const std::string name = need(i), chs = need(i), rate = need(i), in = need(i), outp = need(i);
@@ -1239,6 +1316,19 @@ int run(int argc, char **argv) {
             if (!pcm_format_by_name(*o.output_format) && *o.output_format != "input")
                 throw std::runtime_error("--output-format takes f32, u8, i16, i24, i32 or input, not " + *o.output_format);
         }
+        else if (a == "--dither") {
+            const std::string v = need(i);
+            if (v != "none" && v != "tpdf" && v != "tpdf-hp") throw std::runtime_error("--dither takes none, tpdf or tpdf-hp, not " + v);
+            o.dither = v == "tpdf" ? RC_DITHER_TPDF : v == "tpdf-hp" ? RC_DITHER_TPDF_HP : RC_DITHER_NONE;
+            o.dither_given = true;
+        }
+        else if (a == "--dither-seed") {
+            const std::string v = need(i);
+            char *end = nullptr;
+            const unsigned long long t = strtoull(v.c_str(), &end, 0);
+            if (v.empty() || *end || v[0] == '-') throw std::runtime_error("--dither-seed takes an unsigned integer, not " + v);
+            o.dither_seed = t;
+        }
         else if (a == "--normalize") {
             const std::string v = need(i);
             char *end = nullptr;
@@ -1298,6 +1388,14 @@ int run(int argc, char **argv) {
     if (o.channel_map && !o.frames_on_gpu) throw std::runtime_error("--channel-map needs --frames-on-gpu");
     // (the channels are measured by the engine on the raw frame block, and the copy is the engine's channel map)
     if (o.split_mono && !o.frames_on_gpu) throw std::runtime_error("--split-mono needs --frames-on-gpu");
+    if (o.dither_seed && !o.dither_given) throw std::runtime_error("--dither-seed needs --dither");
+    // dither belongs in front of a quantiser of 8, 16 or 24 bits: f32 has none, and a step of i32 lies below an f32's precision
+    auto check_dither_format = [&](uint32_t fmt) {
+        if (o.dither != RC_DITHER_NONE && fmt != RC_PCM_U8 && fmt != RC_PCM_I16 && fmt != RC_PCM_I24)
+            throw std::runtime_error("--dither needs --output-format u8, i16 or i24 (or input, of such a file)");
+    };
+    if (!o.output_format) check_dither_format(RC_PCM_F32);
+    else if (*o.output_format != "input") check_dither_format(pcm_format_by_name(*o.output_format));
     if (o.frames_on_gpu) {
         // one engine call computes the whole job: nothing polls a watched kernel between windows, and the frame block is
         // neither sharded nor reordered
@@ -1361,6 +1459,7 @@ int run(int argc, char **argv) {
     const bool out_fmt_given = o.output_format.has_value();
     const uint32_t out_fmt = !out_fmt_given ? (uint32_t)RC_PCM_F32 : *o.output_format == "input" ? (o.frames_on_gpu ? raw.format : in_format)
                                                                                            : pcm_format_by_name(*o.output_format);
+    check_dither_format(out_fmt);  // (--output-format input: known only now)
     auto report_clipped = [&](uint64_t clipped, uint64_t samples) {
         if ((out_fmt_given || o.normalize) && clipped) fprintf(stderr, "%llu of %llu samples clipped\n", (unsigned long long)clipped, (unsigned long long)samples);
     };
@@ -1494,6 +1593,11 @@ int run(int argc, char **argv) {
             else if (in_fits) fprintf(stderr, "fade in %zu frames\n", fade);
             else if (out_fits) fprintf(stderr, "fade out from %zu over %zu\n", expected - fade, fade);
         }
+        if (o.dither != RC_DITHER_NONE) {
+            if (!frames_api().set_dither) throw std::runtime_error("--dither: the engine library has no rc_engine_set_output_dither");
+            if (frames_api().set_dither(eng.h, o.dither, o.dither_seed.value_or(o.seed)) != RC_OK)
+                throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+        }
         PinnedBytes out(cap * spec.channels * out_sb);
         size_t n = 0;
         uint64_t clipped = 0;
@@ -1531,6 +1635,7 @@ int run(int argc, char **argv) {
         report_clipped(clipped, total);
         return 0;
     }
+    const HostDither host_dither(o.dither, o.dither_seed.value_or(o.seed), spec.channels);  // the writers' quantiser below
     if (!o.devices.empty()) {
         // several GPUs: the whole job at once through the multi-device entry (windows of a channel are independent
         // given the phase source, so the devices share nothing but the input; include/rocoder_hip.h, rc_multi_*).
@@ -1565,7 +1670,7 @@ int run(int argc, char **argv) {
         for (auto &c : out.data) c.resize(n);
         lap("stretch");
         uint64_t clipped = 0;
-        write_wav(*o.output, out, out_fmt, out_fmt_given ? &clipped : nullptr);
+        write_wav(*o.output, out, out_fmt, out_fmt_given ? &clipped : nullptr, &host_dither);
         lap("write output");
         report_clipped(clipped, (uint64_t)n * spec.channels);
         return 0;
@@ -1605,12 +1710,13 @@ int run(int argc, char **argv) {
         if (!proc.error.empty()) throw std::runtime_error(proc.error);
         lap("stretch");
         uint64_t clipped = 0;
-        write_wav(*o.output, out, out_fmt, out_fmt_given ? &clipped : nullptr);
+        write_wav(*o.output, out, out_fmt, out_fmt_given ? &clipped : nullptr, &host_dither);
         lap("write output");
         report_clipped(clipped, (out.data.empty() ? 0 : (uint64_t)out.data[0].size()) * spec.channels);
         return 0;
     }
     WavStreamWriter wav(*o.output, spec, out_fmt, out_fmt_given);
+    wav.dither = host_dither;
     drain_to_wav(wav, bus);
     for (auto &q : bus) q->abandon();  // (only matters after a `stuck` exit: the processor must not block on a full queue)
     proc.join();

@@ -54,8 +54,8 @@ struct FramesPackParams {
 //   I24  S 8388608     [-8388608, 8388607]  the low 3 bytes
 //   I32  S 2147483647  [-2^31, 2^31 - 1]    4 bytes ((float)S is 2^31: clamped in float to +-2^31, then saturated)
 //   F32  the bits as they are
-// S is the reader's divisor, so decode(encode(.)) is the identity on what the reader gives for u8 / i16 / i24. No
-// dither and no noise shaping: out of scope. *clipped (device memory) grows by the number of samples with
+// S is the reader's divisor, so decode(encode(.)) is the identity on what the reader gives for u8 / i16 / i24. These
+// launchers add no dither: that is launch_frames_pack_pcm_dither / _gain_dither below. *clipped (device memory) grows by the number of samples with
 // !(|x| <= 1) - beyond full scale or NaN, whatever the format - by one atomic per workgroup that saw any.
 // The launch writes the n_frames * channels * bytes bytes of its frames and no other byte, each once and without
 // reading the target: a launch for the frames in front or behind may run, or be downloaded, at the same time.
@@ -99,6 +99,31 @@ struct FramesPackPcmGainParams {
     FramesNormWords *norm;
     float target_peak;
     uint32_t store_gain;
+};
+
+// The dither in front of the quantiser (rc_engine_set_output_dither; the definition is stated in include/rocoder_hip.h).
+// Row c of the launch is job channel channel0 + c, frame f of the launch is absolute output frame t = t0 + f, and
+// keys[channel0 + c] is that channel's key K = rc_phase_key(seed, channel0 + c, 0xFFFFFFFFFF): `keys` is the JOB's device
+// table, of which the launch reads the entries [channel0, channel0 + channels). With h(c, t) = rc_phase_hash(K(c), t mod 2^32):
+//   mode 1 (TPDF)     i = (int)(h >> 16) - (int)(h & 0xFFFF)
+//   mode 2 (TPDF_HP)  i = (int)(h(c, t) >> 16) - (int)(h(c, t - 1) >> 16)        (t - 1 mod 2^32: at t = 0 the counter 0xFFFFFFFF)
+//   d = (float)i * 2^-16;  t1 = x * (float)S;  t2 = t1 + d, ONE IEEE addition, no fma;  r = rint(t2), NaN -> 0, clamped
+// with S, LO, HI of FramesPackPcmParams and x behind the gain where there is one. *clipped counts on x, in front of the
+// dither. U8, I16 and I24 only; any other format or mode is refused. A sample gets the d of its own (c, t) whichever
+// workgroup or launch encodes it: the bytes do not depend on how a job is cut into tiles or launches.
+struct FramesDitherParams {
+    uint32_t mode;      // 1 or 2: RC_DITHER_TPDF, RC_DITHER_TPDF_HP
+    uint32_t channel0;
+    uint64_t t0;
+    const uint64_t *keys;
+};
+struct FramesPackPcmDitherParams {
+    FramesPackPcmParams pack;
+    FramesDitherParams dither;
+};
+struct FramesPackPcmGainDitherParams {
+    FramesPackPcmGainParams gain;
+    FramesDitherParams dither;
 };
 
 // The output fade (rc_engine_set_output_fade; the definition is stated in include/rocoder_hip.h), in place on planar rows.
@@ -173,6 +198,8 @@ hipError_t launch_frames_pack(const FramesPackParams &p, hipStream_t s);
 hipError_t launch_frames_pack_pcm(uint32_t format, const FramesPackPcmParams &p, hipStream_t s);
 hipError_t launch_frames_peak(const FramesPeakParams &p, hipStream_t s);
 hipError_t launch_frames_pack_pcm_gain(uint32_t format, const FramesPackPcmGainParams &p, hipStream_t s);
+hipError_t launch_frames_pack_pcm_dither(uint32_t format, const FramesPackPcmDitherParams &p, hipStream_t s);
+hipError_t launch_frames_pack_pcm_gain_dither(uint32_t format, const FramesPackPcmGainDitherParams &p, hipStream_t s);
 hipError_t launch_frames_fade(const FramesFadeParams &p, hipStream_t s);  // (nothing is launched for t1 <= t0)
 hipError_t launch_frames_power(uint32_t format, const FramesPowerParams &p, hipStream_t s);
 hipError_t launch_frames_unpack_map(uint32_t format, const FramesUnpackMapParams &p, hipStream_t s);

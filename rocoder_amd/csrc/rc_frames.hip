@@ -160,6 +160,35 @@ __device__ __forceinline__ uint32_t pcm_encode(float x) {
 
 __device__ __forceinline__ uint32_t pcm_is_clipped(float x) { return !(fabsf(x) <= 1.0f) ? 1u : 0u; }
 
+// pcm_encode with the dither d in front of rint (rc_engine_set_output_dither): t1 = x * S, t2 = t1 + d, one IEEE operation
+// each and never one fma (see below). U8, I16 and I24 only: the other two formats take no dither.
+template <uint32_t FMT>
+__device__ __forceinline__ uint32_t pcm_encode_dithered(float x, float d) {
+    static_assert(FMT == PCM_U8 || FMT == PCM_I16 || FMT == PCM_I24, "no dither on i32 and f32");
+    constexpr float S = FMT == PCM_U8 ? 127.0f : FMT == PCM_I16 ? 32767.0f : 8388608.0f;
+    constexpr float LO = FMT == PCM_U8 ? -128.0f : FMT == PCM_I16 ? -32768.0f : -8388608.0f;
+    constexpr float HI = FMT == PCM_U8 ? 127.0f : FMT == PCM_I16 ? 32767.0f : 8388607.0f;
+    float t1 = __fmul_rn(x, S);
+    // (the build contracts a * b + c wherever it sees one, through __fmul_rn / __fadd_rn too: the empty statement keeps
+    // the rounded product, and d = i * 2^-16, in registers of their own, so that the addition below is an addition)
+    asm volatile("" : "+v"(t1), "+v"(d));
+    float r = rintf(__fadd_rn(t1, d));
+    if (r != r) r = 0.0f;
+    r = fminf(fmaxf(r, LO), HI);
+    const int32_t n = (int32_t)r;
+    return FMT == PCM_U8 ? (uint32_t)(n + 128) : (uint32_t)n;
+}
+
+// rc_phase_hash's mixer (rc_engine.cpp; rc_dev.hpp phase_hash_x) on x = counter * mul + k0
+__device__ __forceinline__ uint32_t dither_hash_x(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x21F0AAADu;
+    x ^= x >> 15;
+    x *= 0x735A2D97u;
+    x ^= x >> 15;
+    return x;
+}
+
 // `q` holds one encoded sample per dword. The byte `rel` bytes into the stream of their low B bytes each ...
 template <uint32_t B>
 __device__ __forceinline__ uint32_t stream_byte(const uint32_t *q, uint32_t rel) {
@@ -223,6 +252,52 @@ __device__ __forceinline__ Gain gain_of(const FramesPackPcmGainParams &p) {
     return Gain{g};
 }
 
+// The dither is a third policy, beside the gain: what turns a sample x of row c at frame f of the launch into its code.
+// NoDither is pcm_encode and looks at neither c nor f: the undithered instantiations are the kernels they were. Dither
+// adds d(c, t) of the sample's OWN job channel and absolute frame, whichever tile quantises it (a tile re-quantises the
+// up to three samples in front of it that its first dword starts with): the bytes do not depend on the tiling.
+struct NoDither {
+    struct Row {
+        template <uint32_t FMT>
+        __device__ __forceinline__ uint32_t encode(float x, uint32_t) const { return pcm_encode<FMT>(x); }
+    };
+    __device__ __forceinline__ Row row(uint32_t) const { return Row{}; }
+    __device__ __forceinline__ Row wave_row(uint32_t) const { return Row{}; }
+};
+struct Dither {
+    const uint64_t *keys;  // of the launch's row 0 on
+    uint32_t t0, hp;       // the launch's frame 0 mod 2^32 (the counter is t mod 2^32); TPDF_HP
+    struct Row {
+        uint32_t mul, x0, hp;  // the hash's x at the launch's frame f: f * mul + x0
+        template <uint32_t FMT>
+        __device__ __forceinline__ uint32_t encode(float x, uint32_t f) const {
+            const uint32_t xt = f * mul + x0, h = dither_hash_x(xt);
+            // TPDF_HP: the counter one back is x - mul, at t = 0 the counter 0xFFFFFFFF as well (all mod 2^32)
+            const int i = hp ? (int)(h >> 16) - (int)(dither_hash_x(xt - mul) >> 16) : (int)(h >> 16) - (int)(h & 0xFFFFu);
+            return pcm_encode_dithered<FMT>(x, (float)i * (1.0f / 65536.0f));
+        }
+    };
+    __device__ __forceinline__ Row row(uint32_t c) const {
+        const uint64_t k = keys[c];
+        const uint32_t mul = (uint32_t)(k >> 32) | 1u;
+        return Row{mul, t0 * mul + (uint32_t)k, hp};
+    }
+    // row(c) where c is the same in every lane of the wave (the wide kernel's main loop: a wave per channel): said so, the
+    // key is one scalar load and mul and x0 are formed once per wave, not once per lane
+    __device__ __forceinline__ Row wave_row(uint32_t c) const { return row(__builtin_amdgcn_readfirstlane(c)); }
+};
+__host__ __device__ __forceinline__ const FramesPackPcmParams &pack_of(const FramesPackPcmDitherParams &p) { return p.pack; }
+__host__ __device__ __forceinline__ const FramesPackPcmParams &pack_of(const FramesPackPcmGainDitherParams &p) { return p.gain.pack; }
+__device__ __forceinline__ NoGain gain_of(const FramesPackPcmDitherParams &) { return NoGain{}; }
+__device__ __forceinline__ Gain gain_of(const FramesPackPcmGainDitherParams &p) { return gain_of(p.gain); }
+__device__ __forceinline__ NoDither dither_of(const FramesPackPcmParams &) { return NoDither{}; }
+__device__ __forceinline__ NoDither dither_of(const FramesPackPcmGainParams &) { return NoDither{}; }
+__device__ __forceinline__ Dither dither_of(const FramesDitherParams &d) {
+    return Dither{d.keys + d.channel0, (uint32_t)d.t0, d.mode == 2u ? 1u : 0u};
+}
+__device__ __forceinline__ Dither dither_of(const FramesPackPcmDitherParams &p) { return dither_of(p.dither); }
+__device__ __forceinline__ Dither dither_of(const FramesPackPcmGainDitherParams &p) { return dither_of(p.dither); }
+
 // LDS: 1024 frames of 8 channels + the frames in front that the first dword starts with (at most 3 bytes: 3 + channels
 // samples at the most)
 constexpr uint32_t kPcmLdsDwords = kNarrowFrames * kNarrowChannels + 16;
@@ -237,6 +312,7 @@ __global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_kernel(PP pp) 
     const uint64_t f0 = (uint64_t)blockIdx.x * kNarrowFrames;
     if (f0 >= p.n_frames) return;
     const auto gain = gain_of(pp);
+    const auto dither = dither_of(pp);
     if (tid == 0) clip_sum = 0;
     __syncthreads();
     const uint32_t tf = (uint32_t)(p.n_frames - f0 < kNarrowFrames ? p.n_frames - f0 : kNarrowFrames);
@@ -251,9 +327,11 @@ __global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_kernel(PP pp) 
     uint32_t nclip = 0;
     for (uint32_t c = 0; c < C; ++c) {
         const float *row = p.planar + (uint64_t)c * p.stride + (f0 - lead);
+        const auto enc = dither.row(c);
+        const uint32_t fr = (uint32_t)f0 - lead;  // the launch's frame of lds[0] (a launch has at most 2^27)
         for (uint32_t fl = tid; fl < sf; fl += kFramesThreads) {
             const float x = gain(row[fl]);
-            lds[fl * C + c] = pcm_encode<FMT>(x);
+            lds[fl * C + c] = enc.template encode<FMT>(x, fr + fl);
             if (fl >= lead) nclip += pcm_is_clipped(x);  // (a frame in front is counted by its own tile)
         }
     }
@@ -294,6 +372,7 @@ __global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_wide_kernel(PP
     const uint32_t c0 = blockIdx.y * kWideChannels;
     if (f0 >= p.n_frames || c0 >= C) return;
     const auto gain = gain_of(pp);
+    const auto dither = dither_of(pp);
     if (tid == 0) clip_sum = 0;
     __syncthreads();
     const uint32_t tf = (uint32_t)(p.n_frames - f0 < kWideFrames ? p.n_frames - f0 : kWideFrames);
@@ -303,7 +382,7 @@ __global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_wide_kernel(PP
     if (lane < tf)
         for (uint32_t c = wave; c < tc; c += kWaves) {
             const float x = gain(p.planar[(uint64_t)(c0 + c) * p.stride + f0 + lane]);
-            lds[lane * kPcmWidePitch + 3 + c] = pcm_encode<FMT>(x);
+            lds[lane * kPcmWidePitch + 3 + c] = dither.wave_row(c0 + c).template encode<FMT>(x, (uint32_t)f0 + lane);
             nclip += pcm_is_clipped(x);
         }
     // the samples in front of a row's segment that its first dword starts with: sample e back ends at g0 - (e - 1) B
@@ -313,7 +392,7 @@ __global__ __launch_bounds__(kFramesThreads) void frames_pack_pcm_wide_kernel(PP
         if (g0 - (e - 1u) * B > first) {  // (then it is a sample of the launch: its last byte is at or behind T)
             const uint64_t f = c0 >= e ? f0 + r : f0 + r - 1;
             const uint32_t c = c0 >= e ? c0 - e : C + c0 - e;
-            lds[r * kPcmWidePitch + 3 - e] = pcm_encode<FMT>(gain(p.planar[(uint64_t)c * p.stride + f]));
+            lds[r * kPcmWidePitch + 3 - e] = dither.row(c).template encode<FMT>(gain(p.planar[(uint64_t)c * p.stride + f]), (uint32_t)f);
         }
     }
     add_clipped(nclip, &clip_sum, p.clipped);
@@ -716,6 +795,19 @@ inline FramesPackPcmParams &pack_of(FramesPackPcmParams &p) { return p; }
 inline FramesPackPcmParams &pack_of(FramesPackPcmGainParams &p) { return p.pack; }
 inline void next_launch(FramesPackPcmParams &) {}
 inline void next_launch(FramesPackPcmGainParams &p) { p.store_gain = 0; }
+inline FramesPackPcmParams &pack_of(FramesPackPcmDitherParams &p) { return p.pack; }
+inline FramesPackPcmParams &pack_of(FramesPackPcmGainDitherParams &p) { return p.gain.pack; }
+inline void next_launch(FramesPackPcmDitherParams &) {}
+inline void next_launch(FramesPackPcmGainDitherParams &p) { p.gain.store_gain = 0; }
+// a launch's absolute frame 0: the job's t0 + the frames of the launches in front of it (the dithered blocks only)
+inline void launch_frame0(FramesPackPcmParams &, uint64_t) {}
+inline void launch_frame0(FramesPackPcmGainParams &, uint64_t) {}
+inline void launch_frame0(FramesPackPcmDitherParams &p, uint64_t t0) { p.dither.t0 = t0; }
+inline void launch_frame0(FramesPackPcmGainDitherParams &p, uint64_t t0) { p.dither.t0 = t0; }
+inline uint64_t frame0_of(const FramesPackPcmParams &) { return 0; }
+inline uint64_t frame0_of(const FramesPackPcmGainParams &) { return 0; }
+inline uint64_t frame0_of(const FramesPackPcmDitherParams &p) { return p.dither.t0; }
+inline uint64_t frame0_of(const FramesPackPcmGainDitherParams &p) { return p.dither.t0; }
 
 template <uint32_t FMT, class PP>
 hipError_t pack_pcm_fmt(const PP &pp, hipStream_t s) {
@@ -732,6 +824,7 @@ hipError_t pack_pcm_fmt(const PP &pp, hipStream_t s) {
         q.phase = (uint32_t)(off & 3u);
         q.n_frames = p.n_frames - done < kMaxFramesPerLaunch ? p.n_frames - done : kMaxFramesPerLaunch;
         if (done) next_launch(qq);
+        launch_frame0(qq, frame0_of(pp) + done);
         const uint32_t tiles = (uint32_t)((q.n_frames + per - 1) / per);
         if (narrow) {
             frames_pack_pcm_kernel<FMT, PP><<<dim3(tiles), dim3(kFramesThreads), 0, s>>>(qq);
@@ -907,6 +1000,40 @@ hipError_t launch_frames_pack_pcm_gain(uint32_t format, const FramesPackPcmGainP
     case PCM_I24: return pack_pcm_fmt<PCM_I24>(pp, s);
     case PCM_I32: return pack_pcm_fmt<PCM_I32>(pp, s);
     default: return pack_pcm_fmt<PCM_F32>(pp, s);
+    }
+}
+
+namespace {
+bool dither_ok(uint32_t format, const FramesPackPcmParams &p, const FramesDitherParams &d) {
+    return (d.mode == 1u || d.mode == 2u) && d.keys && (uint64_t)d.channel0 + p.channels <= 65535u &&
+           (format == PCM_U8 || format == PCM_I16 || format == PCM_I24);
+}
+}  // namespace
+
+hipError_t launch_frames_pack_pcm_dither(uint32_t format, const FramesPackPcmDitherParams &pp, hipStream_t s) {
+    const FramesPackPcmParams &p = pp.pack;
+    if (!pcm_bytes(format)) return hipErrorInvalidValue;
+    if (p.n_frames == 0) return hipSuccess;
+    if (p.channels == 0 || p.channels > 65535u || p.phase > 3u || ((uintptr_t)p.target & 3u) || !p.clipped || !dither_ok(format, p, pp.dither))
+        return hipErrorInvalidValue;
+    switch (format) {
+    case PCM_U8: return pack_pcm_fmt<PCM_U8>(pp, s);
+    case PCM_I16: return pack_pcm_fmt<PCM_I16>(pp, s);
+    default: return pack_pcm_fmt<PCM_I24>(pp, s);
+    }
+}
+
+hipError_t launch_frames_pack_pcm_gain_dither(uint32_t format, const FramesPackPcmGainDitherParams &pp, hipStream_t s) {
+    const FramesPackPcmParams &p = pp.gain.pack;
+    if (!pcm_bytes(format)) return hipErrorInvalidValue;
+    if (p.n_frames == 0) return hipSuccess;
+    if (p.channels == 0 || p.channels > 65535u || p.phase > 3u || ((uintptr_t)p.target & 3u) || !p.clipped || !pp.gain.norm ||
+        !(pp.gain.target_peak > 0.0f && pp.gain.target_peak < __builtin_inff()) || !dither_ok(format, p, pp.dither))
+        return hipErrorInvalidValue;
+    switch (format) {
+    case PCM_U8: return pack_pcm_fmt<PCM_U8>(pp, s);
+    case PCM_I16: return pack_pcm_fmt<PCM_I16>(pp, s);
+    default: return pack_pcm_fmt<PCM_I24>(pp, s);
     }
 }
 

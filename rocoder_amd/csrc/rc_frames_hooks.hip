@@ -44,6 +44,17 @@ int rc_test_frames_pack_pcm_gain(uint32_t format, const float *planar, uint64_t 
         nullptr));
 }
 
+// (norm null: launch_frames_pack_pcm_dither; else launch_frames_pack_pcm_gain_dither)
+int rc_test_frames_pack_pcm_dither(uint32_t format, const float *planar, uint64_t stride, unsigned char *target, uint32_t phase,
+                                   uint32_t channels, uint64_t n_frames, uint64_t *clipped, rc::FramesNormWords *norm, float target_peak,
+                                   uint32_t store_gain, uint32_t mode, uint64_t t0, uint32_t channel0, const uint64_t *keys) {
+    const rc::FramesPackPcmParams pk{planar, stride, target, phase, channels, n_frames, clipped};
+    const rc::FramesDitherParams di{mode, channel0, t0, keys};
+    return finish(norm ? rc::launch_frames_pack_pcm_gain_dither(
+                             format, rc::FramesPackPcmGainDitherParams{rc::FramesPackPcmGainParams{pk, norm, target_peak, store_gain}, di}, nullptr)
+                       : rc::launch_frames_pack_pcm_dither(format, rc::FramesPackPcmDitherParams{pk, di}, nullptr));
+}
+
 int rc_test_frames_peak(const float *planar, uint64_t stride, uint64_t n_frames, uint32_t channels, rc::FramesNormWords *norm) {
     return finish(rc::launch_frames_peak(rc::FramesPeakParams{planar, stride, n_frames, channels, norm}, nullptr));
 }

@@ -629,6 +629,19 @@ class Engine:
                 raise ValueError("fade frame counts are unsigned 64-bit integers")
         self._check(self._L.rc_engine_set_output_fade(self._h, int(fade_in), start, int(fade_out_len)))
 
+    def set_output_dither(self, mode: str = "none", seed: int = 0):
+        """Dither in front of the integer quantiser of `stretch_frames(out_fmt="u8" | "i16" | "i24")`, with or without
+        `normalize` (rc_engine_set_output_dither; the definition is in include/rocoder_hip.h): "tpdf" is triangular noise
+        of 2 LSB peak to peak, "tpdf-hp" the same triangle high-passed, "none" (the default) clears it. The dither of
+        a sample depends on `seed`, its channel and its output frame alone. i32 and f32 output, the f32 result,
+        `stretch_host`, the device and streaming calls and MultiEngine are untouched. An unknown mode raises and the
+        previous state stays."""
+        if mode not in _lib.DITHER_MODES:
+            raise ValueError(f"dither mode {mode!r} is none of {sorted(_lib.DITHER_MODES)}")
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("the dither seed is an unsigned 64-bit integer")
+        self._check(self._L.rc_engine_set_output_dither(self._h, _lib.DITHER_MODES[mode], int(seed)))
+
     def set_device_kernel_params(self, params: Sequence[float]):
         """Up to 16 floats, h.param(i) in the kernel; they take effect from the next call."""
         arr, n = _params_array(params)
