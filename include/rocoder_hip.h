@@ -294,6 +294,49 @@ int rc_engine_set_output_fade(rc_engine *e, uint64_t in_len, uint64_t out_start,
 #define RC_DITHER_TPDF 1
 #define RC_DITHER_TPDF_HP 2
 int rc_engine_set_output_dither(rc_engine *e, uint32_t mode, uint64_t seed);
+/* Band-limited resampling of the result by a rational step: fractional pitch and a change of the output's sample rate.
+ * `-p/--pitch_multiple` moves the pitch by octaves only and, for p > 1, drops samples with no filter in front
+ * (src/resampler.rs:15-18). With a resampler, pitch by a ratio r is the classic construction: an engine created with
+ * factor * r, then a step of r input frames per output frame - the duration stays factor * L and every frequency is
+ * multiplied by r; a change of sample rate is the step rate_in / rate_out; the two compose into one ratio. The step is
+ * engine state, set once, like the fade, the channel map and the dither:
+ *   num / den  the step, the input frames advanced per output frame. The setter reduces it by the gcd. num == den clears
+ *              it, 0 / 0 clears it too; cleared is the state after rc_engine_create.
+ *   RC_EINVAL  a null engine, exactly one of the two zero, reduced den > 1024, num > 8 * den or den > 8 * num. The previous
+ *              state stays.
+ * The definition. x[c][k], k in [0, n), is the engine's planar f32 result - what rc_engine_stretch_host gives with no
+ * step set - and zero outside [0, n). Z = 32, beta = 9, roll-off 0.9, num / den reduced:
+ *   s = min(1, den / num);  c = 0.9 * s;  W = Z where num <= den, else ceil(Z * num / den);  T = 2 W taps
+ *   n_rs = 0 for n = 0, else floor((n * den - 1) / num) + 1: the m with m * num / den < n      (rc_resample_len)
+ *   for output frame m, in 64-bit integers:  q = floor(m * num / den);  p = (m * num) mod den;  k0 = q - (W - 1)
+ *   table row p, tap j in [0, T):  u = j - (W - 1) - p / den;
+ *       h[p][j] = c * sinc(c u) * I0(beta * sqrt(1 - (u / W)^2)) / I0(beta)  for |u| < W, else 0;  sinc(v) = sin(pi v) / (pi v)
+ *       computed in f64 on the host and rounded once to f32                                      (rc_resample_table)
+ *   y[c][m] = sum over j of h[p][j] * x[c][k0 + j] in f32: ONE chain acc = fmaf(h[p][j], x[c][k0 + j], acc) from +0 with j
+ *       ascending. The order depends on (p, j) alone: a sample's bits do not depend on which tile, launch or pipeline
+ *       chunk computed it.
+ * The filter (the f32 table, for steps from 1/8 to 8): within +-0.00025 dB of 1 up to 0.8 * s of the input's Nyquist
+ * frequency, at least 91 dB down from s * Nyquist upward, every row sums to 1 within 8e-6, sum over j of |h[p][j]| <= 2.24.
+ * y takes the place of x in everything downstream, and all of it counts resampled frames: the positions of the output
+ * fade, the peak and the gain of rc_engine_stretch_frames_norm, the dither's frame counter, the count of clipped
+ * samples, out_cap / out_cap_frames (RC_ECAPACITY below n_rs) and *out_len / *out_frames_len.
+ * Reach: the four whole-job host-form entries, as the fade - rc_engine_stretch_host, rc_engine_stretch_frames, _pcm and
+ * _norm, under a host frequency kernel as well. The device-form entries (rc_engine_stretch_device,
+ * rc_engine_stretch_device_range), the streaming seam (rc_engine_next_window ...) and rc_multi IGNORE it: they return
+ * what they return without it. With the state cleared every byte of every entry is what it is without this entry.
+ * rc_offline_output_len stays the length of x: a caller sizes a resampled output with rc_resample_len of it. */
+int rc_engine_set_output_resample(rc_engine *e, uint32_t num, uint32_t den);
+/* Pure host helpers of the resampler: no device is touched.
+ * rc_resample_len: n_rs as stated above for rows of n frames (0 where num or den is 0).
+ * rc_resample_table: the table the engine uploads for num / den, *phases = the reduced den rows of *taps = T floats each,
+ *   row p at table[p * T]. RC_EINVAL for a step the setter refuses (num == den is the step 1 here) or a null size
+ *   pointer; RC_ECAPACITY where cap < den * T floats, the sizes still stored; table == NULL returns the sizes only.
+ * rc_resample_ratio: the best rational num / den of `step` with den <= 1024 (continued fractions on the exact value of
+ *   the f32: its 6e-8 is 1e-4 cents), inside the setter's limits. RC_EINVAL for a step outside [1/8, 8] or not finite, or
+ *   a null pointer; *num and *den are then left as they were. */
+size_t rc_resample_len(size_t n, uint32_t num, uint32_t den);
+int rc_resample_table(uint32_t num, uint32_t den, float *table, size_t cap, uint32_t *phases, uint32_t *taps);
+int rc_resample_ratio(float step, uint32_t *num, uint32_t *den);
 /* The reference's autocrop (src/recorder.rs:146-191, applied to a recording in front of `-s/-d`, src/main.rs:173-181):
  * the peak of every bin of a block of frames, measured on the device on the raw block, and the crop points those peaks
  * give. Three entries; a caller cuts by pointer arithmetic - the frames entries above take frames at any byte alignment.

@@ -94,6 +94,12 @@ extern "C" {
     pub fn rc_engine_set_output_fade(e: *mut RcEngine, in_len: u64, out_start: u64, out_len: u64) -> c_int;  // RC_FADE_NONE = u64::MAX
     // dither in front of the u8 / i16 / i24 quantiser of the two entries above: RC_DITHER_*, counter-based on (seed, channel, frame)
     pub fn rc_engine_set_output_dither(e: *mut RcEngine, mode: u32, seed: u64) -> c_int;
+    // band-limited resampling of the result by the step num / den input frames per output frame (fractional pitch, a change
+    // of sample rate): engine state like the fade; num == den or 0 / 0 clears it. The helpers touch no device.
+    pub fn rc_engine_set_output_resample(e: *mut RcEngine, num: u32, den: u32) -> c_int;
+    pub fn rc_resample_len(n: usize, num: u32, den: u32) -> usize;
+    pub fn rc_resample_table(num: u32, den: u32, table: *mut f32, cap: usize, phases: *mut u32, taps: *mut u32) -> c_int;
+    pub fn rc_resample_ratio(step: f32, num: *mut u32, den: *mut u32) -> c_int;
     // the reference's autocrop (src/recorder.rs:94-113,146-191): per-bin peaks of the raw block, then the crop points
     pub fn rc_frames_power_bins(n_frames: usize, bin_frames: u64) -> usize;
     pub fn rc_engine_frames_power(e: *mut RcEngine, frames: *const c_void, n_frames: usize, format: u32,

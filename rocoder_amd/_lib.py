@@ -115,6 +115,10 @@ SYMBOLS = {
                                                 C.POINTER(C.c_uint64)]),
     "rc_engine_set_output_fade": (C.c_int, [_eng, C.c_uint64, C.c_uint64, C.c_uint64]),
     "rc_engine_set_output_dither": (C.c_int, [_eng, C.c_uint32, C.c_uint64]),
+    "rc_engine_set_output_resample": (C.c_int, [_eng, C.c_uint32, C.c_uint32]),
+    "rc_resample_len": (_sz, [_sz, C.c_uint32, C.c_uint32]),
+    "rc_resample_table": (C.c_int, [C.c_uint32, C.c_uint32, _fp, _sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rc_resample_ratio": (C.c_int, [C.c_float, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rc_frames_power_bins": (_sz, [_sz, C.c_uint64]),
     "rc_engine_frames_power": (C.c_int, [_eng, C.c_void_p, _sz, C.c_uint32, C.c_uint64, C.POINTER(C.c_float), _sz,
                                          C.POINTER(_sz)]),

@@ -191,6 +191,11 @@ struct FramesApi {
     decltype(&rc_engine_set_channel_map) set_map = nullptr;  // (--channel-map / --split-mono only: may be missing)
     decltype(&rc_engine_frames_channel_peaks) channel_peaks = nullptr;  // (--split-mono only: may be missing, both or neither)
     decltype(&rc_split_mono_map) split_map = nullptr;
+    // (--pitch-ratio / --pitch-cents / --output-rate only: may be missing, all or none)
+    decltype(&rc_engine_set_output_resample) set_resample = nullptr;
+    decltype(&rc_resample_ratio) resample_ratio = nullptr;
+    decltype(&rc_resample_len) resample_len = nullptr;
+    decltype(&rc_resample_table) resample_table = nullptr;
     decltype(&rc_host_alloc) alloc = nullptr;
     decltype(&rc_host_free) free = nullptr;
 };
@@ -207,6 +212,10 @@ static const FramesApi &frames_api() {
         a.set_map = (decltype(a.set_map))dlsym(RTLD_DEFAULT, "rc_engine_set_channel_map");
         a.channel_peaks = (decltype(a.channel_peaks))dlsym(RTLD_DEFAULT, "rc_engine_frames_channel_peaks");
         a.split_map = (decltype(a.split_map))dlsym(RTLD_DEFAULT, "rc_split_mono_map");
+        a.set_resample = (decltype(a.set_resample))dlsym(RTLD_DEFAULT, "rc_engine_set_output_resample");
+        a.resample_ratio = (decltype(a.resample_ratio))dlsym(RTLD_DEFAULT, "rc_resample_ratio");
+        a.resample_len = (decltype(a.resample_len))dlsym(RTLD_DEFAULT, "rc_resample_len");
+        a.resample_table = (decltype(a.resample_table))dlsym(RTLD_DEFAULT, "rc_resample_table");
         a.alloc = (decltype(a.alloc))dlsym(RTLD_DEFAULT, "rc_host_alloc");
         a.free = (decltype(a.free))dlsym(RTLD_DEFAULT, "rc_host_free");
         if (!a.stretch || !a.alloc || !a.free) throw std::runtime_error("--frames-on-gpu: the engine library has no rc_engine_stretch_frames");
@@ -1114,6 +1123,10 @@ struct Opt {  // src/main.rs:27-122
     // recorder::auto_split_mono (src/recorder.rs:118-144, in front of the autocrop, :64-70): measured on the GPU (--frames-on-gpu)
     bool split_mono = false;
     std::optional<float> normalize;  // not in the reference: the output's peak is brought to this level on the GPU (--frames-on-gpu)
+    // not in the reference (-p moves octaves, and decimates with no filter): pitch by any ratio and another output rate, by
+    // band-limited resampling of the result on the GPU (--frames-on-gpu; rc_engine_set_output_resample)
+    std::optional<double> pitch_ratio;  // --pitch-ratio, or 2^(c / 1200) of --pitch-cents
+    std::optional<uint32_t> output_rate;
     // not in the reference (it writes f32): dither in front of the u8 / i16 / i24 quantiser, on the GPU under --frames-on-gpu
     // and in the writer otherwise - the same bytes
     uint32_t dither = RC_DITHER_NONE;
@@ -1161,6 +1174,12 @@ void usage() {
             "        --normalize <peak>             With --frames-on-gpu: measure the peak of the whole output on the GPU and scale\n"
             "                                       it to <peak> (1 = full scale) in front of the quantiser, any --output-format;\n"
             "                                       peak and gain are reported\n"
+            "        --pitch-ratio <a/b | decimal>  With --frames-on-gpu: multiply every frequency by the ratio (1/8 ... 8) and keep\n"
+            "                                       the duration: the stretch runs at factor * ratio and the result is resampled,\n"
+            "                                       band-limited, on the GPU. Composes with -p\n"
+            "        --pitch-cents <c>              The same with the ratio 2^(c / 1200): 100 is a semitone up\n"
+            "        --output-rate <Hz>             With --frames-on-gpu: write the output at this sample rate (resampled on the\n"
+            "                                       GPU in the same pass as --pitch-ratio); the pitch and the duration stay\n"
             "    -p, --pitch_multiple <n>           A non-zero integer pitch multiplier [default: 1]\n"
             "    -s, --start <start>                Start time in input audio (hh:mm:ss.ss)\n"
             "    -w, --window <window-len>          Processing window size [default: 16384]\n"
@@ -1337,6 +1356,30 @@ int run(int argc, char **argv) {
                 throw std::runtime_error("--normalize takes a finite peak level above 0, not " + v);
             o.normalize = t;
         }
+        else if (a == "--pitch-ratio" || a == "--pitch-cents") {
+            if (o.pitch_ratio) throw std::runtime_error("--pitch-ratio and --pitch-cents: one of them, once");
+            const std::string v = need(i);
+            char *end = nullptr;
+            double r = strtod(v.c_str(), &end);
+            if (a == "--pitch-ratio" && end != v.c_str() && *end == '/') {  // a/b
+                const std::string den = end + 1;
+                const double d = strtod(den.c_str(), &end);
+                r = den.empty() || *end ? NAN : r / d;
+            } else if (v.empty() || *end) {
+                r = NAN;
+            } else if (a == "--pitch-cents") {
+                r = std::exp2(r / 1200.0);
+            }
+            if (!(r >= 0.125 && r <= 8.0)) throw std::runtime_error(a + " takes a ratio of 1/8 ... 8 (3600 cents either way), not " + v);
+            o.pitch_ratio = r;
+        }
+        else if (a == "--output-rate") {
+            const std::string v = need(i);
+            char *end = nullptr;
+            const unsigned long t = strtoul(v.c_str(), &end, 10);
+            if (v.empty() || *end || v[0] == '-' || t == 0 || t > 0xFFFFFFFFul) throw std::runtime_error("--output-rate takes a sample rate in Hz, not " + v);
+            o.output_rate = (uint32_t)t;
+        }
         else if (a == "--freq-kernel") o.freq_kernel = need(i);
         else if (a == "--device-kernel") o.device_kernel = need(i);
         else if (a == "--device-kernel-src") o.device_kernel_src = need(i);
@@ -1382,6 +1425,9 @@ int run(int argc, char **argv) {
     if (o.normalize && !o.frames_on_gpu) throw std::runtime_error("--normalize needs --frames-on-gpu");
     // (the fade is applied by the engine's whole-job calls: the streamed host writer has no such step)
     if (o.fade_output && !o.frames_on_gpu) throw std::runtime_error("--fade-output needs --frames-on-gpu");
+    // (the resampler is a stage of the engine's whole-job calls: the streamed host writer has no such step)
+    if (o.pitch_ratio && !o.frames_on_gpu) throw std::runtime_error("--pitch-ratio / --pitch-cents needs --frames-on-gpu");
+    if (o.output_rate && !o.frames_on_gpu) throw std::runtime_error("--output-rate needs --frames-on-gpu");
     // (the bins are measured by the engine on the raw frame block: the host reader has decoded it by then)
     if (o.autocrop && !o.frames_on_gpu) throw std::runtime_error("--autocrop needs --frames-on-gpu");
     // (the map is an index in the engine's unpack kernel; the host path has --rotate-channels)
@@ -1480,7 +1526,9 @@ int run(int argc, char **argv) {
     rc_config cfg{};
     cfg.struct_size = sizeof cfg;
     cfg.window_len = (uint32_t)o.window_len;
-    cfg.factor = o.factor;
+    // --pitch-ratio r: the stretch runs at factor * r and the result is resampled by r input frames per output frame, so
+    // that the duration stays factor * L and every frequency is multiplied by r
+    cfg.factor = o.pitch_ratio ? (float)((double)o.factor * *o.pitch_ratio) : o.factor;
     cfg.amplitude = o.amplitude;
     cfg.pitch_multiple = o.pitch_multiple;
     cfg.sample_rate = spec.sample_rate;
@@ -1575,15 +1623,33 @@ int run(int argc, char **argv) {
             clip_raw();
             lap("autocrop");
         }
-        const size_t cap = rc_offline_output_len(&cfg, raw_count);
+        size_t cap = rc_offline_output_len(&cfg, raw_count);
         const uint32_t out_sb = pcm_sample_bytes(out_fmt);
+        AudioSpec out_spec = spec;  // the output file's: --output-rate
+        if (o.pitch_ratio || o.output_rate) {
+            // one step for both: r input frames per output frame for the pitch, rate_in / rate_out for the rate
+            const FramesApi &api = frames_api();
+            if (!api.set_resample || !api.resample_ratio || !api.resample_len || !api.resample_table)
+                throw std::runtime_error("--pitch-ratio / --pitch-cents / --output-rate: the engine library has no rc_engine_set_output_resample");
+            out_spec.sample_rate = o.output_rate.value_or(spec.sample_rate);
+            const double asked = o.pitch_ratio.value_or(1.0) * (double)spec.sample_rate / (double)out_spec.sample_rate;
+            uint32_t num = 0, den = 0, phases = 0, taps = 0;
+            if (api.resample_ratio((float)asked, &num, &den) != RC_OK || api.resample_table(num, den, nullptr, 0, &phases, &taps) != RC_OK ||
+                api.set_resample(eng.h, num, den) != RC_OK)
+                throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+            fprintf(stderr, "resample %u/%u (%+.4f cents off %.9g), %u taps\n", num, den, 1200.0 * std::log2((double)num / (double)den / asked), asked,
+                    taps);
+            if (num != den) cap = api.resample_len(cap, num, den);
+        }
         if (o.fade_output) {
             // Layer::fade_in_out (src/mixer.rs:179-190) in frames: the fade-in over the first F frames, the fade-out over
             // the F frames in front of expected_total_samples (src/main.rs:154); Audio::fade_*_at_sample's bounds checks
             // and warnings (src/audio.rs:82-85,101-104) decide here, so that the engine call cannot fail on them
             if (!frames_api().set_fade) throw std::runtime_error("--fade-output: the engine library has no rc_engine_set_output_fade");
-            const size_t fade = (size_t)((float)((double)o.fade_ms / 1000.0) * (float)spec.sample_rate);
-            const size_t expected = (size_t)((float)raw_count * o.factor);
+            // (in frames of the output file: at --output-rate, and of factor * L whatever the pitch ratio)
+            const size_t fade = (size_t)((float)((double)o.fade_ms / 1000.0) * (float)out_spec.sample_rate);
+            size_t expected = (size_t)((float)raw_count * o.factor);
+            if (out_spec.sample_rate != spec.sample_rate) expected = (size_t)((double)expected * (double)out_spec.sample_rate / (double)spec.sample_rate);
             const bool in_fits = fade <= cap, out_fits = expected <= cap && expected >= fade;
             if (!in_fits) fprintf(stderr, "Fade in parameters out of bounds, ignoring.\n");
             if (!out_fits) fprintf(stderr, "Fade out parameters out of bounds, ignoring.\n");
@@ -1620,9 +1686,9 @@ int run(int argc, char **argv) {
         const std::string tmp = *o.output + ".part";
         FILE *g = fopen(tmp.c_str(), "wb");
         if (!g) throw std::runtime_error("cannot create " + tmp);
-        write_wav_header(g, spec, n, out_fmt);
+        write_wav_header(g, out_spec, n, out_fmt);
         const size_t total = n * spec.channels;
-        const bool ok = fwrite(out.p, out_sb, total, g) == total && write_wav_pad(g, spec, n, out_fmt);
+        const bool ok = fwrite(out.p, out_sb, total, g) == total && write_wav_pad(g, out_spec, n, out_fmt);
         if (fclose(g) != 0 || !ok) {
             (void)std::remove(tmp.c_str());
             throw std::runtime_error("write failed (disk full?)");

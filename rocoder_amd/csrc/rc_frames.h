@@ -192,6 +192,31 @@ struct FramesChannelPeaksParams {
     uint32_t *chan_bits;
 };
 
+// Band-limited resampling of planar rows by the step num/den input frames per output frame (rc_engine_set_output_resample;
+// the definition is stated in include/rocoder_hip.h; not the reference's `-p < 0` interpolation, which is ResampleParams /
+// launch_resample_slower of rc_kernels.h). x[c][k] is the job's row c, k in [0, n), zero outside. For output frame m, in
+// 64-bit integers: q = m * num / den, p = (m * num) mod den, k0 = q - (W - 1), and
+//   y[c][m] = sum over j < 2 W of table[p * 2 W + j] * x[c][k0 + j]
+// as ONE chain acc = fmaf(table[..j], x[k0 + j], acc) from acc = +0 with j ascending: a sample's bits do not depend on
+// the tile, the launch or the range that computed it. `src` is the sample of the first channel at absolute input frame
+// src0, of which src_len frames are readable per row (rows `stride` floats apart); `dst` the sample of the first channel
+// at output frame m0 (rows dst_stride apart). The launch writes the frames [m0, m1) of every channel and nothing else.
+// `table` is the device copy of rc_resample_table's den x 2 W floats (8-byte aligned), num/den reduced, W <= 256.
+// The launcher refuses (hipErrorInvalidValue, nothing launched) a range one of whose taps lies inside [0, n) but outside
+// [src0, src0 + src_len). Nothing is launched for m1 <= m0; more than 2^27 outputs go out as several launches.
+struct FramesResampleParams {
+    const float *src;
+    uint64_t src0, src_len;
+    uint64_t stride;
+    uint32_t channels;
+    uint64_t n;
+    const float *table;
+    uint32_t num, den, W;
+    float *dst;
+    uint64_t dst_stride;
+    uint64_t m0, m1;
+};
+
 // (all: nothing is launched for n_frames == 0; a job of more than 2^27 frames goes out as several launches)
 hipError_t launch_frames_unpack(uint32_t format, const FramesUnpackParams &p, hipStream_t s);
 hipError_t launch_frames_pack(const FramesPackParams &p, hipStream_t s);
@@ -204,5 +229,6 @@ hipError_t launch_frames_fade(const FramesFadeParams &p, hipStream_t s);  // (no
 hipError_t launch_frames_power(uint32_t format, const FramesPowerParams &p, hipStream_t s);
 hipError_t launch_frames_unpack_map(uint32_t format, const FramesUnpackMapParams &p, hipStream_t s);
 hipError_t launch_frames_channel_peaks(uint32_t format, const FramesChannelPeaksParams &p, hipStream_t s);
+hipError_t launch_frames_resample(const FramesResampleParams &p, hipStream_t s);  // (rc_frames_resample.hip)
 
 }  // namespace rc

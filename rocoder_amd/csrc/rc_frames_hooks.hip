@@ -64,4 +64,11 @@ int rc_test_frames_fade(float *planar, uint64_t stride, uint32_t channels, uint6
     return finish(rc::launch_frames_fade(rc::FramesFadeParams{planar, stride, channels, in_len, out_start, out_len, t0, t1}, nullptr));
 }
 
+int rc_test_frames_resample(const float *src, uint64_t src0, uint64_t src_len, uint64_t stride, uint32_t channels, uint64_t n,
+                            const float *table, uint32_t num, uint32_t den, uint32_t W, float *dst, uint64_t dst_stride, uint64_t m0,
+                            uint64_t m1) {
+    return finish(rc::launch_frames_resample(
+        rc::FramesResampleParams{src, src0, src_len, stride, channels, n, table, num, den, W, dst, dst_stride, m0, m1}, nullptr));
+}
+
 }  // extern "C"

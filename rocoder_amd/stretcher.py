@@ -212,6 +212,37 @@ def offline_output_len(in_len: int, **kw) -> int:
     return int(_lib.lib().rc_offline_output_len(C.byref(cfg), in_len))
 
 
+def resample_len(n: int, num: int, den: int) -> int:
+    """The frames a resample of `n` frames by the step num / den gives (rc_resample_len): the m with m * num / den < n."""
+    if not (0 <= int(n) < 2 ** 64 and 0 <= int(num) < 2 ** 32 and 0 <= int(den) < 2 ** 32):
+        raise ValueError("n, num and den are unsigned integers")
+    return int(_lib.lib().rc_resample_len(int(n), int(num), int(den)))
+
+
+def resample_table(num: int, den: int) -> np.ndarray:
+    """The filter table the engine uploads for the step num / den (rc_resample_table; the definition is in
+    include/rocoder_hip.h): float32 [reduced den, T], row p the T = 2 W coefficients of phase p. Pure host code. A step
+    `Engine.set_output_resample` refuses raises (RC_EINVAL)."""
+    if not (0 <= int(num) < 2 ** 32 and 0 <= int(den) < 2 ** 32):
+        raise ValueError("num and den are unsigned 32-bit integers")
+    L = _lib.lib()
+    phases, taps = C.c_uint32(0), C.c_uint32(0)
+    check(L.rc_resample_table(int(num), int(den), None, 0, C.byref(phases), C.byref(taps)), L)
+    out = np.empty((phases.value, taps.value), np.float32)
+    check(L.rc_resample_table(int(num), int(den), _fp(out), out.size, C.byref(phases), C.byref(taps)), L)
+    return out
+
+
+def resample_ratio(step: float):
+    """(num, den): the best rational of float32(`step`) with den <= 1024 (rc_resample_ratio, continued fractions) - what
+    `Engine.set_output_resample` takes for a pitch ratio r and a change of rate, step = r * rate_in / rate_out. A step
+    outside [1/8, 8] or not finite raises (RC_EINVAL)."""
+    L = _lib.lib()
+    num, den = C.c_uint32(0), C.c_uint32(0)
+    check(L.rc_resample_ratio(float(step), C.byref(num), C.byref(den)), L)
+    return int(num.value), int(den.value)
+
+
 def autocrop_points(bin_peak, bin_frames: int, n_frames: int, percentile: int = 30):
     """The reference's crop points (determine_noise_threshold + determine_autocrop_points, src/recorder.rs:165-191) from
     the peaks `Engine.frames_power` gives: (start, end) in frames - the job's frames [start, end) are what remains - or
@@ -291,6 +322,7 @@ class Engine:
         self._check(self._L.rc_engine_get_params(self._h, C.byref(self.params)))
         self.channels = int(self._cfg.channels)
         self.window_len = int(self._cfg.window_len)
+        self._resample = None  # set_output_resample: (num, den) while a step is set
 
     def close(self):
         for o in list((getattr(self, "_views", None) or {}).values()):
@@ -374,6 +406,11 @@ class Engine:
     def output_len(self, in_len: int) -> int:
         return int(self._L.rc_offline_output_len(C.byref(self._cfg), in_len))
 
+    def _host_output_len(self, in_len: int) -> int:
+        # what `stretch_host` and `stretch_frames` give: output_len, resampled where a step is set
+        n = self.output_len(in_len)
+        return n if self._resample is None else int(self._L.rc_resample_len(n, *self._resample))
+
     def stretch_host(self, channels_in, out: Optional[np.ndarray] = None) -> np.ndarray:
         """Host arrays in, host arrays out (rc_engine_stretch_host). `out` (float32 [channels, >= output_len], rows
         contiguous) is filled and returned when given - reuse it across calls, and allocate both sides with
@@ -383,7 +420,7 @@ class Engine:
             x = np.ascontiguousarray(x, dtype=np.float32)
         if x.shape[0] != self.channels:
             raise ValueError("channel count mismatch")
-        n_out = self.output_len(x.shape[1])
+        n_out = self._host_output_len(x.shape[1])
         if out is None:
             out = np.empty((self.channels, n_out), np.float32)
         elif (out.dtype != np.float32 or out.ndim != 2 or out.shape[0] != self.channels or out.shape[1] < n_out
@@ -453,7 +490,7 @@ class Engine:
             if out_fmt is None:
                 out_fmt = "f32"
         raw, code, n = self._raw_frames(frames, fmt)
-        n_out = self.output_len(n)
+        n_out = self._host_output_len(n)
         if out_fmt is not None:
             if out_fmt not in _lib.PCM_FORMATS:
                 raise ValueError(f"out_fmt must be one of {sorted(_lib.PCM_FORMATS)}")
@@ -641,6 +678,19 @@ class Engine:
         if not 0 <= int(seed) < 2 ** 64:
             raise ValueError("the dither seed is an unsigned 64-bit integer")
         self._check(self._L.rc_engine_set_output_dither(self._h, _lib.DITHER_MODES[mode], int(seed)))
+
+    def set_output_resample(self, num: int = 0, den: int = 0):
+        """Band-limited resampling of the result of `stretch_host` and `stretch_frames` on the GPU by the step num / den
+        input frames per output frame (rc_engine_set_output_resample; the definition is in include/rocoder_hip.h): a
+        pitch ratio r on an engine created with factor * r, a change of sample rate as rate_in / rate_out, or both in
+        one ratio (`resample_ratio`). The result has `resample_len(output_len(n), num, den)` frames, and the fade, the
+        peak, the gain, the dither and the clipped count work on resampled frames. num == den (the defaults included)
+        clears it. `output_len`, `stretch_device`, the streaming calls and MultiEngine are untouched. A step outside
+        [1/8, 8] or with a reduced denominator above 1024 raises (RC_EINVAL) and the previous state stays."""
+        if not (0 <= int(num) < 2 ** 32 and 0 <= int(den) < 2 ** 32):
+            raise ValueError("num and den are unsigned 32-bit integers")
+        self._check(self._L.rc_engine_set_output_resample(self._h, int(num), int(den)))
+        self._resample = None if int(num) == int(den) else (int(num), int(den))
 
     def set_device_kernel_params(self, params: Sequence[float]):
         """Up to 16 floats, h.param(i) in the kernel; they take effect from the next call."""
