@@ -337,6 +337,49 @@ int rc_engine_set_output_resample(rc_engine *e, uint32_t num, uint32_t den);
 size_t rc_resample_len(size_t n, uint32_t num, uint32_t den);
 int rc_resample_table(uint32_t num, uint32_t den, float *table, size_t cap, uint32_t *phases, uint32_t *taps);
 int rc_resample_ratio(float step, uint32_t *num, uint32_t *den);
+/* A look-ahead peak limiter in front of the PCM quantiser: the third answer to an over, beside the quantiser's hard clip
+ * (*clipped) and rc_engine_stretch_frames_norm's one gain for the whole file. It turns the gain down smoothly around an
+ * over and leaves every other frame bit for bit as it was. The offline form is fully parallel - a sliding-window minimum
+ * of the required gain followed by a sliding-window mean - and with the gain in fixed point both are integer operations:
+ * the result does not depend on evaluation order, tiling or chunking. The limiter is engine state, set once, like the
+ * fade, the map, the dither and the step:
+ *   ceiling == 0.0f clears it, whatever the other arguments are; cleared is the state after rc_engine_create.
+ *   RC_EINVAL  otherwise: a null engine, a drive that is not finite or not > 0, a ceiling that is not finite or not > 0,
+ *              lookahead > RC_LIMITER_MAX_LOOKAHEAD. The previous state stays.
+ * The definition, bit for bit. x[c][t], t in [0, n), is the planar f32 result behind the resampler, where one is set, and
+ * behind the fade. L = lookahead, T = 2 L + 1, ONE = 2^24. Every float step is ONE correctly rounded IEEE f32 operation,
+ * not contracted with its neighbours:
+ *   v[c][t] = x[c][t] * drive
+ *   a[t]    the largest |v[c][t]| over the channels c whose |v| is < inf: NaN and +-inf are skipped, as the normaliser's
+ *           peak skips them; 0 where no channel qualifies. The limiter is channel-linked: one gain per frame.
+ *   r[t]    ceiling / a[t] where a[t] > ceiling, else 1.0f
+ *   rq[t]   (uint32_t)(r[t] * 16777216.0f): the product is exact, the conversion truncates, rq lies in [0, ONE]. For t
+ *           outside [0, n), rq[t] = ONE.
+ *   m[u]    the minimum of rq[t] over |t - u| <= L, for u in [-L, n + L)
+ *   S[t]    the sum of m[u] over |u - t| <= L, as a 64-bit integer: exact and below 2^37
+ *   g[t]    (float)S[t] / (float)(T * ONE): S converted to f32 with round to nearest even, T * ONE exact in f32, ONE f32
+ *           division. g == 1.0f whenever S == T * ONE.
+ *   y       v[c][t] * g[t]; then y > ceiling gives ceiling, y < -ceiling gives -ceiling, otherwise y stays, and a NaN stays
+ *           a NaN. (The roundings of r, g and the product can leave y one ulp above ceiling: the clamp matters.)
+ * Consequences: each over at frame u0 pulls a triangular notch into the gain, centred on u0, which reaches r[u0] there and
+ * is 1 again from 2 L + 1 frames away; g[t] depends on the frames [t - 2 L, t + 2 L] alone; with drive == 1 every non-NaN
+ * sample with S[t] == T * ONE leaves with the bits it came with; L == 0 is a per-frame gain with no ramp.
+ * y takes the place of x in everything downstream: the peak and the gain of rc_engine_stretch_frames_norm, the dither, the
+ * quantiser, the count of clipped samples, the f32 frames and rows.
+ * Reach: the four whole-job host-form entries, as the fade and the resampler - rc_engine_stretch_host,
+ * rc_engine_stretch_frames, _pcm and _norm, under a host frequency kernel as well. The device forms, the streaming seam,
+ * rc_multi, rc_engine_frames_power and rc_engine_frames_channel_peaks IGNORE it. Cleared, every byte of every entry is
+ * what it is without this entry. A limited job holds one more row buffer of channels x n floats on the device (the fused
+ * kernel needs no scratch beyond it).
+ * rc_engine_last_limiter_stats reports on the last call of one of the four entries that ran with a limiter set (those
+ * calls block: nothing is pending when it is read):
+ *   *min_gain        the smallest g[t]; 1.0f for a job of no frames, and 1.0f where no such call has run
+ *   *limited_frames  the number of frames with S[t] < T * ONE
+ * Either pointer may be NULL; a null engine is RC_EINVAL. Both values are order-free: a minimum of non-negative float bits
+ * and a count. */
+#define RC_LIMITER_MAX_LOOKAHEAD 2048
+int rc_engine_set_output_limiter(rc_engine *e, float drive, float ceiling, uint32_t lookahead);
+int rc_engine_last_limiter_stats(rc_engine *e, float *min_gain, uint64_t *limited_frames);
 /* The reference's autocrop (src/recorder.rs:146-191, applied to a recording in front of `-s/-d`, src/main.rs:173-181):
  * the peak of every bin of a block of frames, measured on the device on the raw block, and the crop points those peaks
  * give. Three entries; a caller cuts by pointer arithmetic - the frames entries above take frames at any byte alignment.

@@ -32,6 +32,7 @@ pub const RC_PCM_F32: u32 = 5;
 pub const RC_DITHER_NONE: u32 = 0;
 pub const RC_DITHER_TPDF: u32 = 1;
 pub const RC_DITHER_TPDF_HP: u32 = 2;
+pub const RC_LIMITER_MAX_LOOKAHEAD: u32 = 2048;
 
 /// `rc_config`: the arguments of `Stretcher::new` (src/stretcher.rs:30-39) for all channels of a job.
 #[repr(C)]
@@ -100,6 +101,8 @@ extern "C" {
     pub fn rc_resample_len(n: usize, num: u32, den: u32) -> usize;
     pub fn rc_resample_table(num: u32, den: u32, table: *mut f32, cap: usize, phases: *mut u32, taps: *mut u32) -> c_int;
     pub fn rc_resample_ratio(step: f32, num: *mut u32, den: *mut u32) -> c_int;
+    pub fn rc_engine_set_output_limiter(e: *mut RcEngine, drive: f32, ceiling: f32, lookahead: u32) -> c_int;
+    pub fn rc_engine_last_limiter_stats(e: *mut RcEngine, min_gain: *mut f32, limited_frames: *mut u64) -> c_int;
     // the reference's autocrop (src/recorder.rs:94-113,146-191): per-bin peaks of the raw block, then the crop points
     pub fn rc_frames_power_bins(n_frames: usize, bin_frames: u64) -> usize;
     pub fn rc_engine_frames_power(e: *mut RcEngine, frames: *const c_void, n_frames: usize, format: u32,

@@ -54,6 +54,7 @@ RC_DK_NONE, RC_DK_GAIN, RC_DK_BAND, RC_DK_SHIFT = 0, 1, 2, 3
 RC_PCM_U8, RC_PCM_I16, RC_PCM_I24, RC_PCM_I32, RC_PCM_F32 = 1, 2, 3, 4, 5
 RC_FADE_NONE = 2**64 - 1  # rc_engine_set_output_fade: no fade-out
 RC_DITHER_NONE, RC_DITHER_TPDF, RC_DITHER_TPDF_HP = 0, 1, 2  # rc_engine_set_output_dither
+RC_LIMITER_MAX_LOOKAHEAD = 2048  # rc_engine_set_output_limiter: the largest look-ahead, in frames
 DITHER_MODES = {"none": RC_DITHER_NONE, "tpdf": RC_DITHER_TPDF, "tpdf-hp": RC_DITHER_TPDF_HP}
 PCM_FORMATS = {"u8": RC_PCM_U8, "i16": RC_PCM_I16, "i24": RC_PCM_I24, "i32": RC_PCM_I32, "f32": RC_PCM_F32}
 PCM_BYTES = {RC_PCM_U8: 1, RC_PCM_I16: 2, RC_PCM_I24: 3, RC_PCM_I32: 4, RC_PCM_F32: 4}
@@ -119,6 +120,8 @@ SYMBOLS = {
     "rc_resample_len": (_sz, [_sz, C.c_uint32, C.c_uint32]),
     "rc_resample_table": (C.c_int, [C.c_uint32, C.c_uint32, _fp, _sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rc_resample_ratio": (C.c_int, [C.c_float, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rc_engine_set_output_limiter": (C.c_int, [_eng, C.c_float, C.c_float, C.c_uint32]),
+    "rc_engine_last_limiter_stats": (C.c_int, [_eng, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
     "rc_frames_power_bins": (_sz, [_sz, C.c_uint64]),
     "rc_engine_frames_power": (C.c_int, [_eng, C.c_void_p, _sz, C.c_uint32, C.c_uint64, C.POINTER(C.c_float), _sz,
                                          C.POINTER(_sz)]),

@@ -196,6 +196,9 @@ struct FramesApi {
     decltype(&rc_resample_ratio) resample_ratio = nullptr;
     decltype(&rc_resample_len) resample_len = nullptr;
     decltype(&rc_resample_table) resample_table = nullptr;
+    // (--limit only: may be missing, both or neither)
+    decltype(&rc_engine_set_output_limiter) set_limiter = nullptr;
+    decltype(&rc_engine_last_limiter_stats) limiter_stats = nullptr;
     decltype(&rc_host_alloc) alloc = nullptr;
     decltype(&rc_host_free) free = nullptr;
 };
@@ -216,6 +219,8 @@ static const FramesApi &frames_api() {
         a.resample_ratio = (decltype(a.resample_ratio))dlsym(RTLD_DEFAULT, "rc_resample_ratio");
         a.resample_len = (decltype(a.resample_len))dlsym(RTLD_DEFAULT, "rc_resample_len");
         a.resample_table = (decltype(a.resample_table))dlsym(RTLD_DEFAULT, "rc_resample_table");
+        a.set_limiter = (decltype(a.set_limiter))dlsym(RTLD_DEFAULT, "rc_engine_set_output_limiter");
+        a.limiter_stats = (decltype(a.limiter_stats))dlsym(RTLD_DEFAULT, "rc_engine_last_limiter_stats");
         a.alloc = (decltype(a.alloc))dlsym(RTLD_DEFAULT, "rc_host_alloc");
         a.free = (decltype(a.free))dlsym(RTLD_DEFAULT, "rc_host_free");
         if (!a.stretch || !a.alloc || !a.free) throw std::runtime_error("--frames-on-gpu: the engine library has no rc_engine_stretch_frames");
@@ -1127,6 +1132,13 @@ struct Opt {  // src/main.rs:27-122
     // band-limited resampling of the result on the GPU (--frames-on-gpu; rc_engine_set_output_resample)
     std::optional<double> pitch_ratio;  // --pitch-ratio, or 2^(c / 1200) of --pitch-cents
     std::optional<uint32_t> output_rate;
+    // not in the reference (an over is clipped by its writer): a look-ahead peak limiter on the result, on the GPU
+    // (--frames-on-gpu; rc_engine_set_output_limiter)
+    std::optional<float> limit;       // --limit: the ceiling, linear
+    float limit_drive = 1.0f;         // --limit-drive
+    bool limit_drive_given = false;
+    uint64_t limit_lookahead_ms = 5;  // --limit-lookahead
+    bool limit_lookahead_given = false;
     // not in the reference (it writes f32): dither in front of the u8 / i16 / i24 quantiser, on the GPU under --frames-on-gpu
     // and in the writer otherwise - the same bytes
     uint32_t dither = RC_DITHER_NONE;
@@ -1180,6 +1192,13 @@ void usage() {
             "        --pitch-cents <c>              The same with the ratio 2^(c / 1200): 100 is a semitone up\n"
             "        --output-rate <Hz>             With --frames-on-gpu: write the output at this sample rate (resampled on the\n"
             "                                       GPU in the same pass as --pitch-ratio); the pitch and the duration stay\n"
+            "        --limit <ceiling | dB>         With --frames-on-gpu: a look-ahead peak limiter on the GPU behind --fade-output and in\n"
+            "                                       front of --normalize, --dither and the quantiser: no sample leaves above the\n"
+            "                                       ceiling (1 = full scale, or -0.3dB), frames away from an over keep their bits;\n"
+            "                                       the frames turned down and the lowest gain are reported\n"
+            "        --limit-drive <gain | dB>      Gain in front of --limit [default: 1]\n"
+            "        --limit-lookahead <dur>        The ramp of --limit to either side of an over, at most 2048 frames of the output\n"
+            "                                       file [default: 0.005]\n"
             "    -p, --pitch_multiple <n>           A non-zero integer pitch multiplier [default: 1]\n"
             "    -s, --start <start>                Start time in input audio (hh:mm:ss.ss)\n"
             "    -w, --window <window-len>          Processing window size [default: 16384]\n"
@@ -1373,6 +1392,24 @@ int run(int argc, char **argv) {
             if (!(r >= 0.125 && r <= 8.0)) throw std::runtime_error(a + " takes a ratio of 1/8 ... 8 (3600 cents either way), not " + v);
             o.pitch_ratio = r;
         }
+        else if (a == "--limit" || a == "--limit-drive") {  // linear, or with a trailing dB
+            const std::string v = need(i);
+            char *end = nullptr;
+            float t = strtof(v.c_str(), &end);
+            const bool db = end != v.c_str() && (std::string(end) == "dB" || std::string(end) == "db");
+            if (db) t = (float)std::pow(10.0, (double)t / 20.0);
+            if (v.empty() || end == v.c_str() || (*end && !db) || !(t > 0.0f) || !std::isfinite(t))
+                throw std::runtime_error(a + " takes a finite level above 0, linear or in dB (-0.3dB), not " + v);
+            if (a == "--limit") o.limit = t;
+            else {
+                o.limit_drive = t;
+                o.limit_drive_given = true;
+            }
+        }
+        else if (a == "--limit-lookahead") {
+            o.limit_lookahead_ms = dur(need(i));
+            o.limit_lookahead_given = true;
+        }
         else if (a == "--output-rate") {
             const std::string v = need(i);
             char *end = nullptr;
@@ -1428,6 +1465,9 @@ int run(int argc, char **argv) {
     // (the resampler is a stage of the engine's whole-job calls: the streamed host writer has no such step)
     if (o.pitch_ratio && !o.frames_on_gpu) throw std::runtime_error("--pitch-ratio / --pitch-cents needs --frames-on-gpu");
     if (o.output_rate && !o.frames_on_gpu) throw std::runtime_error("--output-rate needs --frames-on-gpu");
+    // (the limiter is a stage of the engine's whole-job calls: the streamed host writer has no such step)
+    if (o.limit && !o.frames_on_gpu) throw std::runtime_error("--limit needs --frames-on-gpu");
+    if ((o.limit_drive_given || o.limit_lookahead_given) && !o.limit) throw std::runtime_error("--limit-drive / --limit-lookahead needs --limit");
     // (the bins are measured by the engine on the raw frame block: the host reader has decoded it by then)
     if (o.autocrop && !o.frames_on_gpu) throw std::runtime_error("--autocrop needs --frames-on-gpu");
     // (the map is an index in the engine's unpack kernel; the host path has --rotate-channels)
@@ -1659,6 +1699,17 @@ int run(int argc, char **argv) {
             else if (in_fits) fprintf(stderr, "fade in %zu frames\n", fade);
             else if (out_fits) fprintf(stderr, "fade out from %zu over %zu\n", expected - fade, fade);
         }
+        if (o.limit) {
+            const FramesApi &api = frames_api();
+            if (!api.set_limiter || !api.limiter_stats) throw std::runtime_error("--limit: the engine library has no rc_engine_set_output_limiter");
+            // (in frames of the output file, as the fade: duration_to_sample at --output-rate)
+            const size_t look = (size_t)((float)((double)o.limit_lookahead_ms / 1000.0) * (float)out_spec.sample_rate);
+            if (look > RC_LIMITER_MAX_LOOKAHEAD)
+                throw std::runtime_error("--limit-lookahead is " + std::to_string(look) + " frames at " + std::to_string(out_spec.sample_rate) +
+                                         " Hz, at most " + std::to_string(RC_LIMITER_MAX_LOOKAHEAD));
+            if (api.set_limiter(eng.h, o.limit_drive, *o.limit, (uint32_t)look) != RC_OK)
+                throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+        }
         if (o.dither != RC_DITHER_NONE) {
             if (!frames_api().set_dither) throw std::runtime_error("--dither: the engine library has no rc_engine_set_output_dither");
             if (frames_api().set_dither(eng.h, o.dither, o.dither_seed.value_or(o.seed)) != RC_OK)
@@ -1682,6 +1733,13 @@ int run(int argc, char **argv) {
         } else if (frames_api().stretch(eng.h, raw.data.p + raw_first * frame_bytes, raw_count, raw.format, (float *)out.p, cap, &n) != RC_OK)
             throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
         lap("stretch");
+        if (o.limit) {
+            float min_gain = 1.0f;
+            uint64_t limited = 0;
+            if (frames_api().limiter_stats(eng.h, &min_gain, &limited) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+            fprintf(stderr, "limited %llu of %zu frames, lowest gain %.9g (%.1f dB)\n", (unsigned long long)limited, n, (double)min_gain,
+                    min_gain > 0.0f ? 20.0 * std::log10((double)min_gain) : -INFINITY);
+        }
         // "<path>.part" first, as WavStreamWriter: a failed run leaves no output file
         const std::string tmp = *o.output + ".part";
         FILE *g = fopen(tmp.c_str(), "wb");

@@ -217,6 +217,48 @@ struct FramesResampleParams {
     uint64_t m0, m1;
 };
 
+// The look-ahead peak limiter (rc_engine_set_output_limiter; the definition is stated in include/rocoder_hip.h), from planar
+// rows to planar rows. x[c][t] is the job's row c, t in [0, n). With L the look-ahead, T = 2 L + 1, ONE = 2^24, every float
+// step ONE correctly rounded IEEE f32 operation:
+//   v = x * drive;  a[t] = the largest |v[c][t]| < inf over the channels (NaN, +-inf skipped; 0 where none);
+//   r[t] = ceiling / a[t] where a[t] > ceiling, else 1;  rq[t] = (uint32_t)(r[t] * 2^24), ONE outside [0, n);
+//   m[u] = min rq[t], |t - u| <= L;  S[t] = sum m[u], |u - t| <= L, in 64 bits;  g[t] = (float)S[t] / (float)(T * ONE);
+//   y = v * g[t], clamped to [-ceiling, ceiling], a NaN kept.
+// m and S are integers: a frame's g does not depend on the tile, the launch or the range that computed it. `src` is the
+// sample of the first channel at absolute frame src0, of which src_len frames are readable per row (rows `stride` floats
+// apart); `dst` the sample of the first channel at frame t0 (rows dst_stride apart). The launch writes the frames [t0, t1) of
+// every channel of dst and nothing else; the halo of rq it needs, the frames [t0 - 2 L, t1 + 2 L), it recomputes from src.
+// The launcher refuses (hipErrorInvalidValue, nothing launched) a range that needs a frame inside [0, n) but outside
+// [src0, src0 + src_len). Nothing is launched for t1 <= t0; more than 2^27 frames go out as several launches.
+// `scratch` / scratch_words: device words a launch may use between its passes. The fused kernel of rc_frames_limit.hip keeps
+// rq, m and the prefix sums in LDS and needs none (frames_limit_scratch_words gives 0): null / 0 are accepted.
+// stats: two device words of the engine, reset by the host in front of a job to {the bits of 1.0f, 0}:
+//   min_gain_bits  the bits of the smallest g[t] so far, joined with atomicMin (g >= 0: the unsigned order of the bits is
+//                  the order of the values), one per workgroup that saw a g below 1
+//   limited        the number of frames with S[t] < T * ONE, one atomicAdd per workgroup that saw any. A frame is computed
+//                  by exactly one launch.
+struct FramesLimitWords {
+    uint32_t min_gain_bits;
+    uint32_t reserved;
+    uint64_t limited;
+};
+constexpr uint32_t kLimitMaxLookahead = 2048;  // RC_LIMITER_MAX_LOOKAHEAD
+struct FramesLimitParams {
+    const float *src;
+    uint64_t src0, src_len;
+    uint64_t stride;
+    uint32_t channels;
+    uint64_t n;
+    float drive, ceiling;
+    uint32_t L;
+    float *dst;
+    uint64_t dst_stride;
+    uint64_t t0, t1;
+    uint32_t *scratch;
+    uint64_t scratch_words;
+    FramesLimitWords *stats;
+};
+
 // (all: nothing is launched for n_frames == 0; a job of more than 2^27 frames goes out as several launches)
 hipError_t launch_frames_unpack(uint32_t format, const FramesUnpackParams &p, hipStream_t s);
 hipError_t launch_frames_pack(const FramesPackParams &p, hipStream_t s);
@@ -230,5 +272,7 @@ hipError_t launch_frames_power(uint32_t format, const FramesPowerParams &p, hipS
 hipError_t launch_frames_unpack_map(uint32_t format, const FramesUnpackMapParams &p, hipStream_t s);
 hipError_t launch_frames_channel_peaks(uint32_t format, const FramesChannelPeaksParams &p, hipStream_t s);
 hipError_t launch_frames_resample(const FramesResampleParams &p, hipStream_t s);  // (rc_frames_resample.hip)
+hipError_t launch_frames_limit(const FramesLimitParams &p, hipStream_t s);        // (rc_frames_limit.hip)
+inline uint64_t frames_limit_scratch_words(uint64_t /*frames*/, uint32_t /*L*/) { return 0; }
 
 }  // namespace rc

@@ -71,4 +71,12 @@ int rc_test_frames_resample(const float *src, uint64_t src0, uint64_t src_len, u
         rc::FramesResampleParams{src, src0, src_len, stride, channels, n, table, num, den, W, dst, dst_stride, m0, m1}, nullptr));
 }
 
+int rc_test_frames_limit(const float *src, uint64_t src0, uint64_t src_len, uint64_t stride, uint32_t channels, uint64_t n, float drive,
+                         float ceiling, uint32_t L, float *dst, uint64_t dst_stride, uint64_t t0, uint64_t t1, uint32_t *scratch,
+                         uint64_t scratch_words, rc::FramesLimitWords *stats) {
+    return finish(rc::launch_frames_limit(
+        rc::FramesLimitParams{src, src0, src_len, stride, channels, n, drive, ceiling, L, dst, dst_stride, t0, t1, scratch, scratch_words, stats},
+        nullptr));
+}
+
 }  // extern "C"

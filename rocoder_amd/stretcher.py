@@ -323,6 +323,7 @@ class Engine:
         self.channels = int(self._cfg.channels)
         self.window_len = int(self._cfg.window_len)
         self._resample = None  # set_output_resample: (num, den) while a step is set
+        self._limiter = False  # set_output_limiter: a limiter is set
 
     def close(self):
         for o in list((getattr(self, "_views", None) or {}).values()):
@@ -432,11 +433,21 @@ class Engine:
         got = C.c_size_t(0)
         self._check(self._L.rc_engine_stretch_host(self._h, ins, x.shape[1], outs, out.shape[1], C.byref(got)))
         assert got.value == n_out
+        self._read_limiter_stats()
         return out[:, :n_out]
 
     last_clipped: Optional[int] = None  # stretch_frames(out_fmt=...): output samples beyond full scale (or NaN) of the last call
     last_peak: Optional[float] = None   # stretch_frames(normalize=...): the largest finite |sample| before the gain ...
     last_gain: Optional[float] = None   # ... and the gain it was multiplied by (both np.float32)
+    # stretch_frames / stretch_host while a limiter is set (set_output_limiter): (the smallest gain as np.float32, the
+    # number of frames turned down) of the last call
+    last_limiter_stats: Optional[tuple] = None
+
+    def _read_limiter_stats(self):
+        if self._limiter:
+            g, f = C.c_float(0), C.c_uint64(0)
+            self._check(self._L.rc_engine_last_limiter_stats(self._h, C.byref(g), C.byref(f)))
+            self.last_limiter_stats = (np.float32(g.value), int(f.value))
 
     def _raw_frames(self, frames, fmt):
         """What `stretch_frames` documents for `frames` and `fmt` -> (the block's bytes, the RC_PCM_* code, n_frames)."""
@@ -517,6 +528,7 @@ class Engine:
                     self._h, src, n, code, C.c_void_p(dst.ctypes.data), cap, ocode, C.byref(got), C.byref(clipped)))
             assert got.value == n_out
             self.last_clipped = int(clipped.value)
+            self._read_limiter_stats()
             return dst[:need].view(dtype).reshape((n_out, self.channels) + tail)
         if out is None:
             out = np.empty((n_out, self.channels), np.float32)
@@ -527,6 +539,7 @@ class Engine:
         src = C.c_void_p(raw.ctypes.data if raw.size else out.ctypes.data)  # (no frames: any non-null pointer)
         self._check(self._L.rc_engine_stretch_frames(self._h, src, n, code, _fp(out), out.shape[0], C.byref(got)))
         assert got.value == n_out
+        self._read_limiter_stats()
         return out[:n_out]
 
     def frames_power(self, frames, fmt: Optional[str] = None, bin_frames: int = 4410) -> np.ndarray:
@@ -691,6 +704,22 @@ class Engine:
             raise ValueError("num and den are unsigned 32-bit integers")
         self._check(self._L.rc_engine_set_output_resample(self._h, int(num), int(den)))
         self._resample = None if int(num) == int(den) else (int(num), int(den))
+
+    def set_output_limiter(self, drive: float = 1.0, ceiling: float = 0.0, lookahead: int = 0):
+        """A look-ahead peak limiter on the result of `stretch_host` and `stretch_frames`, on the GPU, behind the resampler
+        and the fade and in front of the peak of `normalize`, the dither and the quantiser (rc_engine_set_output_limiter;
+        the definition is in include/rocoder_hip.h): every sample times `drive`, then a channel-linked gain that keeps
+        every |sample| at or below `ceiling` and ramps over `lookahead` frames to either side of an over; a frame further
+        than 2 * lookahead frames from every over keeps its bits (drive 1). `ceiling=0` (the default) clears it.
+        `last_limiter_stats` is set by those calls while a limiter is set. `stretch_device`, the streaming calls and
+        MultiEngine are untouched. A drive or ceiling that is not finite or not above 0, or a lookahead above 2048, raises
+        (RC_EINVAL) and the previous state stays."""
+        if not 0 <= int(lookahead) < 2 ** 32:
+            raise ValueError("lookahead is an unsigned 32-bit integer")
+        with np.errstate(over="ignore"):
+            d, c = float(np.float32(drive)), float(np.float32(ceiling))
+        self._check(self._L.rc_engine_set_output_limiter(self._h, C.c_float(d), C.c_float(c), int(lookahead)))
+        self._limiter = c != 0.0
 
     def set_device_kernel_params(self, params: Sequence[float]):
         """Up to 16 floats, h.param(i) in the kernel; they take effect from the next call."""
