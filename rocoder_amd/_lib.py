@@ -203,7 +203,7 @@ _hooks = None
 @contextlib.contextmanager
 def hooks_library():
     """Tests / A-B tools: inside the block `lib()` is the test-hook build (it alone honours ROCODER_DIAG,
-    ROCODER_ROUNDS, ROCODER_MIN_RUN, ROCODER_B4_ROUNDS). Engines created inside keep it for their lifetime."""
+    ROCODER_ROUNDS, ROCODER_MIN_RUN, ROCODER_B4_ROUNDS, ROCODER_TAPER). Engines created inside keep it for their lifetime."""
     global _lib, _hooks
     if _hooks is None:
         _hooks = _load(HOOKS_PATH)

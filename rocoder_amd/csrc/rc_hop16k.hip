@@ -22,6 +22,9 @@ namespace {
 //     f3(n) = n + (n >> 5) + (n >> 8) keeps every access pattern at most 2-way conflicted on a few
 //     lanes; it is additive over disjoint bit fields, so each access is a per-thread base VGPR +
 //     an immediate offset.
+#ifndef RC_DRAIN
+#define RC_DRAIN 0
+#endif
 constexpr int f1_idx(int n) { return n + (n >> 5); }
 constexpr int HOP2_XBUF = 8192 + 256 + 32;
 constexpr int HOP2_LDS_FLOAT2 = HOP2_XBUF + 8 + 32 + 256 + 256 + 16 + 24 + 1024;  // 79 232 B
@@ -360,16 +363,18 @@ __global__ __launch_bounds__(256, 3) void hop4_kernel(const HopParams p) {
         // next eighth, which started with the launch). An XCD that runs out takes from the next one's counter.
         unsigned *slot = reinterpret_cast<unsigned *>(lds + SCR);
         if (tid == 0) {
-            const uint32_t total = p.runs_per_channel * p.n_channels;
+            const uint32_t total = p.run_first ? p.runs_total : p.runs_per_channel * p.n_channels;
             unsigned got = 0xFFFFFFFFu;
             {
                 const uint32_t G = (total + 7u) / 8u;
+                const uint32_t *xb = p.run_first + total + 1;  // (the run table's eighths end in a taper each)
                 unsigned xcc;
                 asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
                 for (uint32_t i = 0; i < 8u; ++i) {
-                    const uint32_t xx = (xcc + i) & 7u, lo = xx * G;
+                    const uint32_t xx = (xcc + i) & 7u, lo = p.run_first ? xb[xx] : xx * G;
                     if (lo >= total) continue;
-                    const uint32_t hi = lo + G < total ? lo + G : total;
+                    const uint32_t hi = p.run_first ? xb[xx + 1] : (lo + G < total ? lo + G : total);
+                    if (hi <= lo) continue;
                     const uint32_t t = atomicAdd(p.run_counter + xx, 1u);
                     if (t < hi - lo) {
                         got = lo + t;
@@ -386,16 +391,49 @@ __global__ __launch_bounds__(256, 3) void hop4_kernel(const HopParams p) {
         // every hop behind an s_waitcnt vmcnt(0) (tools/isa_stats.py --spills)
         gr = (uint32_t)__builtin_amdgcn_readfirstlane((int)*reinterpret_cast<volatile unsigned *>(slot));
         __syncthreads();
-        if (gr == 0xFFFFFFFFu) return;  // (more workgroups than runs: cannot happen with the engine's grid)
     }
-    const uint32_t run = gr % p.runs_per_channel;
-    const uint32_t ch = gr / p.runs_per_channel;
-    const int64_t k_begin = p.hop_first + (int64_t)run * p.run_len;
-    int64_t k_end = k_begin + p.run_len;
+#if RC_DRAIN
+    // diagnostic builds only (tests/dev/drain_hop4.py): the 100 MHz clock at ticket time and on the way out, per
+    // workgroup (s_memrealtime: s_memtime counts each XCD's own shader clock, and the XCDs' clocks differ)
+    unsigned long long drain_t0;
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(drain_t0)::"memory");
+    auto drain_stamp = [&]() {
+        if (tid == 0 && p.spec) {
+            unsigned long long t1;
+            unsigned xcc;
+            asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1)::"memory");
+            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+            unsigned long long *dbg = (unsigned long long *)p.spec + 3 * (size_t)blockIdx.x;
+            dbg[0] = drain_t0;
+            dbg[1] = t1;
+            dbg[2] = ((unsigned long long)(xcc & 7u) << 32) | gr;
+        }
+    };
+#else
+    auto drain_stamp = []() {};
+#endif
+    if (gr == 0xFFFFFFFFu) return;  // (more workgroups than runs: cannot happen with the engine's grid)
+    uint32_t ch, k_lo, k_hi, k_all;  // the run: hops [k_lo, k_hi) of the k_all hops of channel ch
+    if (p.run_first) {
+        const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.run_first[gr]);
+        const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.run_first[gr + 1]);
+        k_all = (uint32_t)p.hop_count;
+        ch = a / k_all;
+        k_lo = a - ch * k_all;
+        k_hi = b - ch * k_all;
+    } else {
+        const uint32_t run = gr % p.runs_per_channel;
+        ch = gr / p.runs_per_channel;
+        k_all = p.runs_per_channel * p.run_len;  // (>= hop_count: the last run is cut below)
+        k_lo = run * p.run_len;
+        k_hi = k_lo + p.run_len;
+    }
+    const int64_t k_begin = p.hop_first + (int64_t)k_lo;
+    int64_t k_end = p.hop_first + (int64_t)k_hi;
     if (k_end > p.hop_first + p.hop_count) k_end = p.hop_first + p.hop_count;
     if (k_begin >= k_end) return;
-    const bool stash_first = seam && run > 0;
-    const bool has_next = seam && run + 1 < p.runs_per_channel;
+    const bool stash_first = seam && k_lo > 0;
+    const bool has_next = seam && k_hi < k_all;
     GF xc = (GF)p.x + (size_t)ch * p.in_stride;
     GF xt = (GF)p.xtail + (size_t)ch * p.tail_stride;
     GFW outc = (GFW)p.out + (size_t)ch * p.out_stride;
@@ -945,6 +983,7 @@ __global__ __launch_bounds__(256, 3) void hop4_kernel(const HopParams p) {
             head[q] = __builtin_bit_cast(v2f, __hip_atomic_load(hs + T * q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         store_head(k_end, head);
     }
+    drain_stamp();
 }
 
 }  // namespace
@@ -954,8 +993,9 @@ __global__ __launch_bounds__(256, 3) void hop4_kernel(const HopParams p) {
 // pitch 1, hop2_kernel at other pitches. The test-hook library (RC_TEST_HOOKS) can also run the previous generation
 // (hop3_kernel, rc_hop16k_prev.hip) for A/B runs.
 hipError_t launch_hop16k(const HopParams &p, hipStream_t s) {
-    const dim3 grid(p.runs_per_channel * p.n_channels), block(256);
+    const dim3 grid(p.run_first ? p.runs_total : p.runs_per_channel * p.n_channels), block(256);
     const bool hann = p.hann_rot != nullptr;
+    if (p.run_first && !hann && p.pitch != 1) return hipErrorInvalidValue;  // (the run table is hop4_kernel's alone)
 #if RC_TEST_HOOKS
     if (hann && (p.diag_flags & RC_DIAG_PREV_KERNEL)) return launch_hop16k_prev(p, s);
 #endif

@@ -49,6 +49,12 @@ struct HopParams {
     uint32_t *seam_flag;
     uint32_t *run_counter;  // RC_RUN_COUNTERS words: hop4_kernel keeps one ticket counter per XCD
     uint32_t seam_epoch;
+    // hop4_kernel's run table (the tapered plan; null: run g of a channel is hops [g * run_len, ...) as above): the
+    // launch's runs in ticket order, channel after channel. runs_total + 1 hop offsets - channel c's hops count from
+    // c * hop_count, a channel's end is always a run's end - followed by 9 run indices: XCD x's ticket counter hands
+    // out runs [b[x], b[x + 1]). seam_head / seam_flag are indexed by the position in this table.
+    const uint32_t *run_first;
+    uint32_t runs_total;
     // RC_DK_BAND fused into hop4_kernel's pair stage (band_on): bins lo..lo+span of the real spectrum (0..N/2) are
     // scaled by band_gin, the others by band_gout (both already |.|: the resynthesis takes magnitudes)
     uint32_t band_on, band_lo, band_span;
