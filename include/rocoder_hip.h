@@ -232,6 +232,68 @@ int rc_engine_stretch_frames_pcm(rc_engine *e, const void *frames, size_t n_fram
 int rc_engine_stretch_frames_norm(rc_engine *e, const void *frames, size_t n_frames, uint32_t format, void *out_frames,
                                   size_t out_cap_frames, uint32_t out_format, float target_peak,
                                   size_t *out_frames_len, float *peak, float *gain, uint64_t *clipped);
+/* rc_engine_stretch_frames_pcm with the result loudness-normalised on the device: the integrated loudness of ITU-R BS.1770-4
+ * / EBU R 128 and the true peak of the whole job are measured there, and every sample is multiplied by one gain in front
+ * of the quantiser - the gain that brings the job to target_lufs, or the smaller one that keeps its true peak at
+ * max_true_peak. The same job otherwise: the input and output formats, any byte alignment, pageable or page-locked memory,
+ * blocking. The definition:
+ *   y[c][t]  t in [0, n): the planar f32 result rc_engine_stretch_frames gives under the engine's current state - behind the
+ *            channel map, the resampler, the fade and the limiter where those are set.
+ *   R        sample_rate, 0 meaning rc_config::sample_rate. A caller that set an output-rate step passes the OUTPUT's rate.
+ * K-weighting: two biquads, their coefficients computed in f64 on the host, K = tan(pi f0 / R) per stage.
+ *   stage 1, the shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, Vh = 10^(G / 20),
+ *     Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2;  b0 = (Vh + Vb K / Q + K^2) / a0;  b1 = 2 (K^2 - Vh) / a0;
+ *     b2 = (Vh - Vb K / Q + K^2) / a0;  a1 = 2 (K^2 - 1) / a0;  a2 = (1 - K / Q + K^2) / a0
+ *   stage 2, the high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, b = [1, -2, 1], a1 and a2 as above with its own
+ *     K and Q.
+ *   At R = 48000 these reproduce the table of BS.1770-4 to 3e-16 relative.
+ *   k[c] = stage 2 of stage 1 of y[c], both from a zero state at t = 0.
+ * Sub-block energies: sub = (R + 5) / 10 frames (100 ms); nb = n / sub, a partial tail is not measured;
+ *   e[c][j] = the sum of k[c][t]^2 over t in [j sub, (j + 1) sub).
+ * Integrated loudness, in f64 on the host from the f32 words e:
+ *   400 ms blocks at 75 % overlap: for i in [0, nb - 3), z[c][i] = (e[c][i] + ... + e[c][i + 3]) / (4 sub);
+ *   l[i] = the sum over the channels of z[c][i]: every channel has weight 1. The rows carry no speaker layout: the 1.41 of
+ *   surround channels and the exclusion of an LFE channel are NOT applied.  L(x) = -0.691 + 10 log10(x).
+ *   absolute gate: keep the i with L(l[i]) > -70;  relative gate: G = L(mean of the kept l) - 10, keep those with
+ *   L(l[i]) > G as well;  I = L(mean of the l[i] that passed both);  I = -inf where no block passes or nb < 4.
+ * True peak: u[c][m], m in [0, 4 n), is exactly what rc_engine_set_output_resample's definition gives for the rows y at the
+ *   step num / den = 1 / 4: the f32 table of rc_resample_table(1, 4, ...) (4 rows of 64 taps), the same single fmaf chain
+ *   with j ascending, y zero outside [0, n). tp = the largest of |y[c][t]| and |u[c][m]| among the values with |.| < inf:
+ *   NaN and +-inf are skipped, as the normaliser's peak skips them; 0 where there are none. A maximum of order-fixed
+ *   chains is order-free: tp is defined bit for bit. What the filter limits: it is flat to 0.00025 dB up to 0.8 of Nyquist
+ *   only, and 4 points per sample can miss a tone's crest by a factor of up to cos(pi f / (4 R)): at f = R / 8 that is
+ *   cos(pi / 32), -0.042 dB, and the worst case measured over the phases (tests/test_loudness_host.py) is -0.0419 dB.
+ *   Above 0.8 of Nyquist the reading falls off with the filter.
+ * Gain: gl = (float)pow(10.0, ((double)target_lufs - (double)(float)I) / 20.0), formed from the REPORTED f32 loudness so
+ *   that a caller can reproduce it; gl = 1 where I = -inf.  gc = max_true_peak / tp, ONE f32 division, where
+ *   max_true_peak > 0 and tp > 0; otherwise +inf.  g = min(gl, gc); g = 1 where that is not finite or not > 0.
+ *   z = y * g; the bytes and *clipped are exactly what rc_engine_stretch_frames_norm writes for a gain of g: ONE IEEE
+ *   multiplication, not contracted, then the dither and the quantiser as they stand.
+ * The device computes e in f64 and rounds each word once. A span of sub-blocks starts its recurrence from a zero state
+ * 200 ms in front of it, which differs from the definition by a relative 1.6e-12 of a sub-block's energy; the words are
+ * sums of a fixed order, so a job measured twice gives the same *lufs. A NaN or an inf in y leaves *lufs unspecified.
+ * lufs, true_peak, gain, clipped and out_frames_len may each be NULL. RC_EINVAL: what rc_engine_stretch_frames_pcm rejects;
+ * a target_lufs that is not finite; a max_true_peak that is NaN or negative (0: no ceiling); R < 8000 or R > 768000.
+ * RC_ECAPACITY: out_cap_frames too small. n_frames == 0 is valid and gives lufs -inf, true_peak 0, gain 1, clipped 0. On
+ * any error nothing behind the out-pointers is written.
+ * Reach: as rc_engine_stretch_frames_norm, under a host frequency kernel as well. The job runs in the same two phases with
+ * ONE host round trip between them: channels x nb + 1 words come back, the gate and the gain are formed on the host.
+ *
+ * Pure host helpers, no device touched:
+ * rc_loudness_coeffs: the ten coefficients at sample_rate - b0 b1 b2 a1 a2 of stage 1, then of stage 2 - the f64 values
+ *   rounded once to f32. RC_EINVAL: a null pointer, a rate outside 8000 ... 768000.
+ * rc_loudness_sub_blocks: nb for n_frames at sample_rate; 0 for a rate out of range.
+ * rc_loudness_integrated: I as stated above from the words energy[c * stride + j], j < n_sub, c < channels, rounded once to
+ *   f32 (-inf included). RC_EINVAL: a null pointer (energy may be null with n_sub == 0), channels == 0, stride < n_sub, a
+ *   rate out of range; *lufs is then left as it was. */
+int rc_engine_stretch_frames_loud(rc_engine *e, const void *frames, size_t n_frames, uint32_t format, void *out_frames,
+                                  size_t out_cap_frames, uint32_t out_format, uint32_t sample_rate, float target_lufs,
+                                  float max_true_peak, size_t *out_frames_len, float *lufs, float *true_peak, float *gain,
+                                  uint64_t *clipped);
+int rc_loudness_coeffs(uint32_t sample_rate, float *coeffs);
+size_t rc_loudness_sub_blocks(size_t n_frames, uint32_t sample_rate);
+int rc_loudness_integrated(const float *energy, uint32_t channels, size_t n_sub, size_t stride, uint32_t sample_rate,
+                           float *lufs);
 /* The reference's sqrt fade-in / fade-out (`-x/--fade`, src/main.rs:91-97,206) on the result of the four whole-job
  * host-form entries above - rc_engine_stretch_host, rc_engine_stretch_frames, rc_engine_stretch_frames_pcm and
  * rc_engine_stretch_frames_norm - applied on the device to the planar f32 result, in front of everything that reads it.

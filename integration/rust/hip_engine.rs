@@ -92,6 +92,17 @@ extern "C" {
                                          out_frames: *mut c_void, out_cap_frames: usize, out_format: u32,
                                          target_peak: f32, out_frames_len: *mut usize, peak: *mut f32,
                                          gain: *mut f32, clipped: *mut u64) -> c_int;
+    // the same with the gain from the job's BS.1770 integrated loudness and 4 x oversampled true peak, both measured on the
+    // device; sample_rate is the OUTPUT's (0: the config's), max_true_peak linear (0: no ceiling). The helpers touch no device.
+    pub fn rc_engine_stretch_frames_loud(e: *mut RcEngine, frames: *const c_void, n_frames: usize, format: u32,
+                                         out_frames: *mut c_void, out_cap_frames: usize, out_format: u32,
+                                         sample_rate: u32, target_lufs: f32, max_true_peak: f32,
+                                         out_frames_len: *mut usize, lufs: *mut f32, true_peak: *mut f32,
+                                         gain: *mut f32, clipped: *mut u64) -> c_int;
+    pub fn rc_loudness_coeffs(sample_rate: u32, coeffs: *mut f32) -> c_int;
+    pub fn rc_loudness_sub_blocks(n_frames: usize, sample_rate: u32) -> usize;
+    pub fn rc_loudness_integrated(energy: *const f32, channels: u32, n_sub: usize, stride: usize, sample_rate: u32,
+                                  lufs: *mut f32) -> c_int;
     pub fn rc_engine_set_output_fade(e: *mut RcEngine, in_len: u64, out_start: u64, out_len: u64) -> c_int;  // RC_FADE_NONE = u64::MAX
     // dither in front of the u8 / i16 / i24 quantiser of the two entries above: RC_DITHER_*, counter-based on (seed, channel, frame)
     pub fn rc_engine_set_output_dither(e: *mut RcEngine, mode: u32, seed: u64) -> c_int;

@@ -114,6 +114,12 @@ SYMBOLS = {
     "rc_engine_stretch_frames_norm": (C.c_int, [_eng, C.c_void_p, _sz, C.c_uint32, C.c_void_p, _sz, C.c_uint32, C.c_float,
                                                 C.POINTER(_sz), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                                 C.POINTER(C.c_uint64)]),
+    "rc_engine_stretch_frames_loud": (C.c_int, [_eng, C.c_void_p, _sz, C.c_uint32, C.c_void_p, _sz, C.c_uint32, C.c_uint32,
+                                                C.c_float, C.c_float, C.POINTER(_sz), C.POINTER(C.c_float),
+                                                C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
+    "rc_loudness_coeffs": (C.c_int, [C.c_uint32, _fp]),
+    "rc_loudness_sub_blocks": (_sz, [_sz, C.c_uint32]),
+    "rc_loudness_integrated": (C.c_int, [_fp, C.c_uint32, _sz, _sz, C.c_uint32, _fp]),
     "rc_engine_set_output_fade": (C.c_int, [_eng, C.c_uint64, C.c_uint64, C.c_uint64]),
     "rc_engine_set_output_dither": (C.c_int, [_eng, C.c_uint32, C.c_uint64]),
     "rc_engine_set_output_resample": (C.c_int, [_eng, C.c_uint32, C.c_uint32]),

@@ -184,6 +184,7 @@ struct FramesApi {
     decltype(&rc_engine_stretch_frames) stretch = nullptr;
     decltype(&rc_engine_stretch_frames_pcm) stretch_pcm = nullptr;  // (--output-format only: may be missing)
     decltype(&rc_engine_stretch_frames_norm) stretch_norm = nullptr;  // (--normalize only: may be missing)
+    decltype(&rc_engine_stretch_frames_loud) stretch_loud = nullptr;  // (--loudness / --true-peak only: may be missing)
     decltype(&rc_engine_set_output_fade) set_fade = nullptr;  // (--fade-output only: may be missing)
     decltype(&rc_engine_set_output_dither) set_dither = nullptr;  // (--dither only: may be missing)
     decltype(&rc_engine_frames_power) power = nullptr;        // (--autocrop only: may be missing, both or neither)
@@ -208,6 +209,7 @@ static const FramesApi &frames_api() {
         a.stretch = (decltype(a.stretch))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames");
         a.stretch_pcm = (decltype(a.stretch_pcm))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames_pcm");
         a.stretch_norm = (decltype(a.stretch_norm))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames_norm");
+        a.stretch_loud = (decltype(a.stretch_loud))dlsym(RTLD_DEFAULT, "rc_engine_stretch_frames_loud");
         a.set_fade = (decltype(a.set_fade))dlsym(RTLD_DEFAULT, "rc_engine_set_output_fade");
         a.set_dither = (decltype(a.set_dither))dlsym(RTLD_DEFAULT, "rc_engine_set_output_dither");
         a.power = (decltype(a.power))dlsym(RTLD_DEFAULT, "rc_engine_frames_power");
@@ -1132,6 +1134,9 @@ struct Opt {  // src/main.rs:27-122
     // band-limited resampling of the result on the GPU (--frames-on-gpu; rc_engine_set_output_resample)
     std::optional<double> pitch_ratio;  // --pitch-ratio, or 2^(c / 1200) of --pitch-cents
     std::optional<uint32_t> output_rate;
+    // not in the reference: the output is brought to this integrated loudness (BS.1770 / EBU R 128) on the GPU, its true
+    // peak kept at true_peak (linear; --frames-on-gpu)
+    std::optional<float> loudness, true_peak;
     // not in the reference (an over is clipped by its writer): a look-ahead peak limiter on the result, on the GPU
     // (--frames-on-gpu; rc_engine_set_output_limiter)
     std::optional<float> limit;       // --limit: the ceiling, linear
@@ -1186,6 +1191,12 @@ void usage() {
             "        --normalize <peak>             With --frames-on-gpu: measure the peak of the whole output on the GPU and scale\n"
             "                                       it to <peak> (1 = full scale) in front of the quantiser, any --output-format;\n"
             "                                       peak and gain are reported\n"
+            "        --loudness <LUFS>              With --frames-on-gpu: measure the integrated loudness (ITU-R BS.1770-4 / EBU R 128) and\n"
+            "                                       the true peak of the whole output on the GPU and scale it to <LUFS> in front of\n"
+            "                                       the quantiser, behind --limit and --fade-output; not with --normalize;\n"
+            "                                       loudness, true peak and gain are reported\n"
+            "        --true-peak <level | dB>       With --loudness: the gain stops where the 4x oversampled peak reaches this level\n"
+            "                                       (1 = full scale, or -1dB)\n"
             "        --pitch-ratio <a/b | decimal>  With --frames-on-gpu: multiply every frequency by the ratio (1/8 ... 8) and keep\n"
             "                                       the duration: the stretch runs at factor * ratio and the result is resampled,\n"
             "                                       band-limited, on the GPU. Composes with -p\n"
@@ -1375,6 +1386,23 @@ int run(int argc, char **argv) {
                 throw std::runtime_error("--normalize takes a finite peak level above 0, not " + v);
             o.normalize = t;
         }
+        else if (a == "--loudness") {
+            const std::string v = need(i);
+            char *end = nullptr;
+            const float t = strtof(v.c_str(), &end);
+            if (v.empty() || *end || !std::isfinite(t)) throw std::runtime_error("--loudness takes a finite level in LUFS (-14, -23), not " + v);
+            o.loudness = t;
+        }
+        else if (a == "--true-peak") {  // linear, or with a trailing dB (dBTP)
+            const std::string v = need(i);
+            char *end = nullptr;
+            float t = strtof(v.c_str(), &end);
+            const bool db = end != v.c_str() && (std::string(end) == "dB" || std::string(end) == "db");
+            if (db) t = (float)std::pow(10.0, (double)t / 20.0);
+            if (v.empty() || end == v.c_str() || (*end && !db) || !(t > 0.0f) || !std::isfinite(t))
+                throw std::runtime_error("--true-peak takes a finite level above 0, linear or in dB (-1dB), not " + v);
+            o.true_peak = t;
+        }
         else if (a == "--pitch-ratio" || a == "--pitch-cents") {
             if (o.pitch_ratio) throw std::runtime_error("--pitch-ratio and --pitch-cents: one of them, once");
             const std::string v = need(i);
@@ -1460,6 +1488,10 @@ int run(int argc, char **argv) {
     // the peak of the whole output has to be known before its first sample is written: the streamed host writer never
     // holds the whole output, the engine under --frames-on-gpu does
     if (o.normalize && !o.frames_on_gpu) throw std::runtime_error("--normalize needs --frames-on-gpu");
+    // (the loudness of the whole output as well)
+    if ((o.loudness || o.true_peak) && !o.frames_on_gpu) throw std::runtime_error("--loudness / --true-peak needs --frames-on-gpu");
+    if (o.true_peak && !o.loudness) throw std::runtime_error("--true-peak needs --loudness: it is the ceiling of that gain");
+    if ((o.loudness || o.true_peak) && o.normalize) throw std::runtime_error("--loudness / --true-peak cannot be combined with --normalize: one gain, one rule");
     // (the fade is applied by the engine's whole-job calls: the streamed host writer has no such step)
     if (o.fade_output && !o.frames_on_gpu) throw std::runtime_error("--fade-output needs --frames-on-gpu");
     // (the resampler is a stage of the engine's whole-job calls: the streamed host writer has no such step)
@@ -1547,7 +1579,7 @@ int run(int argc, char **argv) {
                                                                                            : pcm_format_by_name(*o.output_format);
     check_dither_format(out_fmt);  // (--output-format input: known only now)
     auto report_clipped = [&](uint64_t clipped, uint64_t samples) {
-        if ((out_fmt_given || o.normalize) && clipped) fprintf(stderr, "%llu of %llu samples clipped\n", (unsigned long long)clipped, (unsigned long long)samples);
+        if ((out_fmt_given || o.normalize || o.loudness || o.true_peak) && clipped) fprintf(stderr, "%llu of %llu samples clipped\n", (unsigned long long)clipped, (unsigned long long)samples);
     };
     if (!o.frames_on_gpu && (o.start_ms || o.duration_ms)) audio.clip_in_place(o.start_ms, o.duration_ms);
     if (o.rotate_channels) audio.rotate_channels();
@@ -1726,6 +1758,14 @@ int run(int argc, char **argv) {
                                           &n, &peak, &gain, &clipped) != RC_OK)
                 throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
             fprintf(stderr, "peak %.9g, gain %.9g\n", (double)peak, (double)gain);  // (nine digits: the f32 values exactly)
+        } else if (o.loudness || o.true_peak) {  // loudness and true peak measured on the device, one gain in front of the quantiser
+            if (!frames_api().stretch_loud) throw std::runtime_error("--loudness / --true-peak: the engine library has no rc_engine_stretch_frames_loud");
+            float lufs = 0.0f, tp = 0.0f, gain = 1.0f;
+            if (frames_api().stretch_loud(eng.h, raw.data.p + raw_first * frame_bytes, raw_count, raw.format, out.p, cap, out_fmt,
+                                          out_spec.sample_rate, *o.loudness, o.true_peak.value_or(0.0f), &n, &lufs, &tp, &gain, &clipped) != RC_OK)
+                throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+            fprintf(stderr, "loudness %.9g LUFS, true peak %.9g (%.2f dBTP), gain %.9g (%.2f dB)\n", (double)lufs, (double)tp,
+                    tp > 0.0f ? 20.0 * std::log10((double)tp) : -INFINITY, (double)gain, 20.0 * std::log10((double)gain));
         } else if (out_fmt_given) {  // quantised, packed and counted on the device
             if (!frames_api().stretch_pcm) throw std::runtime_error("--output-format: the engine library has no rc_engine_stretch_frames_pcm");
             if (frames_api().stretch_pcm(eng.h, raw.data.p + raw_first * frame_bytes, raw_count, raw.format, out.p, cap, out_fmt, &n, &clipped) != RC_OK)

@@ -7,7 +7,7 @@
 ROOT := ../../..
 CXX  ?= g++
 COMMON := -g -O1 -std=c++17 -Wall -fno-omit-frame-pointer rocoder_cli.cpp -ldl -lpthread
-all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../bin/engine_tsan ../../bin/engine_dk_asan ../../bin/engine_xch_asan ../../bin/engine_frames_asan ../../bin/engine_frames_pcm_asan ../../bin/engine_frames_norm_asan ../../bin/engine_frames_fade_asan ../../bin/engine_frames_power_asan ../../bin/engine_frames_map_asan ../../bin/engine_frames_dither_asan ../../bin/engine_frames_resample_asan ../../bin/engine_frames_limit_asan
+all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../bin/engine_tsan ../../bin/engine_dk_asan ../../bin/engine_xch_asan ../../bin/engine_frames_asan ../../bin/engine_frames_pcm_asan ../../bin/engine_frames_norm_asan ../../bin/engine_frames_fade_asan ../../bin/engine_frames_power_asan ../../bin/engine_frames_map_asan ../../bin/engine_frames_dither_asan ../../bin/engine_frames_resample_asan ../../bin/engine_frames_limit_asan ../../bin/engine_frames_loud_asan
 ../../bin/rocoder_asan: rocoder_cli.cpp $(ROOT)/include/rocoder_hip.h ../../librocoder_hip.so
 	mkdir -p ../../bin
 	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(COMMON) -o $@ -L../.. -lrocoder_hip \
@@ -28,7 +28,7 @@ TSAN := -fsanitize=thread
 ENGINE_HDR := ../rc_kernels.h ../rc_long.h ../rc_frames.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
 # the engine and the stubs: compiled once per sanitizer, linked into every driver's program
 ENGINE_PARTS := rc_engine rc_rtc hip_stub hip_stub_long hip_stub_frames hip_stub_frames_pcm hip_stub_frames_norm \
-    hip_stub_frames_fade hip_stub_frames_power hip_stub_frames_map hip_stub_frames_dither hip_stub_frames_resample hip_stub_frames_limit hip_stub_rtc
+    hip_stub_frames_fade hip_stub_frames_power hip_stub_frames_map hip_stub_frames_dither hip_stub_frames_resample hip_stub_frames_limit hip_stub_frames_loud hip_stub_rtc
 ENGINE_ASAN_OBJ := $(ENGINE_PARTS:%=../../bin/%.asan.o)
 ENGINE_TSAN_OBJ := $(ENGINE_PARTS:%=../../bin/%.tsan.o)
 vpath %.cpp .. $(ROOT)/tests/c
@@ -65,6 +65,8 @@ vpath %.cpp .. $(ROOT)/tests/c
 #                launcher logs [m0, m1), src0 and src_len, reads every tap it may and writes a mark over its range)
 #   frames_limit rc_engine_set_output_limiter on the four whole-job host-form entries (hip_stub_frames_limit.cpp's launcher
 #                logs [t0, t1), src0 and src_len, reads every frame of its halo and writes a mark over its range)
+#   frames_loud  rc_engine_stretch_frames_loud and, with no engine, its host helpers (hip_stub_frames_loud.cpp's two measuring
+#                launchers read every frame and every parameter word the real ones read, log their rows and give fixed answers)
 ../../bin/engine_%_asan: $(ROOT)/tests/c/engine_host_driver_%.cpp $(ENGINE_ASAN_OBJ) $(ENGINE_HDR)
 	$(CXX) $(ASAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_ASAN_OBJ) -o $@ -lpthread -ldl
 ../../bin/engine_%_tsan: $(ROOT)/tests/c/engine_host_driver_%.cpp $(ENGINE_TSAN_OBJ) $(ENGINE_HDR)

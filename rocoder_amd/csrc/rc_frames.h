@@ -3,6 +3,7 @@
 // kernel family and of no family hash (tools/kernel_id.py).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -259,6 +260,101 @@ struct FramesLimitParams {
     FramesLimitWords *stats;
 };
 
+// The two measurements of rc_engine_stretch_frames_loud (the definition is stated in include/rocoder_hip.h), on the finished
+// planar rows of a job: y[c][t] at planar[c * stride + t], t in [0, n). Both read the rows and write nothing to them.
+//
+// K-weighted sub-block energies (rc_frames_loud.hip). The two biquads of BS.1770 as ONE linear system of four states in
+// direct form II transposed, run in f64 on the device (the high-pass's poles lie 3e-4 from the unit circle at 768 kHz: an
+// f32 recurrence loses what the gate is held to):
+//   y1 = b0 x + s1;  s1' = b1 x - a1 y1 + s2;  s2' = b2 x - a2 y1          stage 1, coef[0 ... 4] = b0 b1 b2 a1 a2
+//   y2 = c0 y1 + u1; u1' = c1 y1 - d1 y2 + u2; u2' = c2 y1 - d2 y2         stage 2, coef[5 ... 9] = c0 c1 c2 d1 d2
+// step[k], k < 8, is A^(kLoudRun * 2^k), row-major 4 x 4 over (s1, s2, u1, u2), A the system's state-transition matrix:
+// what 16, 32, ... 2048 frames of silence do to a state. The host forms them in f64 (frames_loud_energy_steps).
+//   energy[c * e_stride + j] = (float)(sum of k[c][t]^2 over t in [j * sub, (j + 1) * sub)), j < nb, nb * sub <= n
+// with k the f64 recurrence started from a zero state at frame max(0, (j0 - kLoudWarm) * sub), j0 the first sub-block of
+// the workgroup's span (frames_loud_span sub-blocks): from frame 0 that is the definition itself, later it differs from it
+// by what the filter has not forgotten in kLoudWarm sub-blocks (200 ms), a relative 1.6e-12 of a sub-block's energy. Every
+// word is written once, by one workgroup, from sums of a fixed order: no atomics, and the span depends on (channels, nb)
+// alone, so two launches on the same rows give the same words. The launcher refuses (hipErrorInvalidValue, nothing
+// launched) sub < kLoudMinSub, nb * sub > n, e_stride < nb. Nothing is launched for nb == 0.
+constexpr uint32_t kLoudRun = 16;       // frames of a lane's run
+constexpr uint32_t kLoudWarm = 2;       // sub-blocks of warm-up in front of a span
+constexpr uint32_t kLoudMinSub = 800;   // the sub-block of 8 kHz, the lowest rate of rc_engine_stretch_frames_loud
+struct FramesLoudEnergyParams {
+    const float *planar;
+    uint64_t stride;
+    uint64_t n;
+    uint32_t channels;
+    uint32_t sub;  // frames of a sub-block
+    uint64_t nb;   // sub-blocks measured
+    float *energy;
+    uint64_t e_stride;
+    double coef[10];
+    double step[8][16];
+};
+// sub-blocks of a workgroup's span: enough workgroups to fill the device on a short job, little warm-up on a long one
+inline uint32_t frames_loud_span(uint32_t channels, uint64_t nb) {
+    const uint64_t s = (uint64_t)channels * nb / 2048u;
+    return (uint32_t)(s < 4u ? 4u : s > 32u ? 32u : s);
+}
+// the ten f64 coefficients at the rate R, as include/rocoder_hip.h states them (rc_loudness_coeffs rounds these); host code
+inline void frames_loud_coeffs(uint32_t R, double coef[10]) {
+    const double kPi = 3.14159265358979323846;
+    {
+        const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+        const double K = std::tan(kPi * f0 / (double)R), Vh = std::pow(10.0, G / 20.0), Vb = std::pow(Vh, 0.4996667741545416);
+        const double a0 = 1.0 + K / Q + K * K;
+        coef[0] = (Vh + Vb * K / Q + K * K) / a0;
+        coef[1] = 2.0 * (K * K - Vh) / a0;
+        coef[2] = (Vh - Vb * K / Q + K * K) / a0;
+        coef[3] = 2.0 * (K * K - 1.0) / a0;
+        coef[4] = (1.0 - K / Q + K * K) / a0;
+    }
+    {
+        const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+        const double K = std::tan(kPi * f0 / (double)R), a0 = 1.0 + K / Q + K * K;
+        coef[5] = 1.0;
+        coef[6] = -2.0;
+        coef[7] = 1.0;
+        coef[8] = 2.0 * (K * K - 1.0) / a0;
+        coef[9] = (1.0 - K / Q + K * K) / a0;
+    }
+}
+// coef and step of a params block from the ten f64 coefficients (b0 b1 b2 a1 a2 of stage 1, then of stage 2); host code.
+// With x = 0: s1' = -a1 s1 + s2; s2' = -a2 s1; u1' = (c1 - d1 c0) s1 - d1 u1 + u2; u2' = (c2 - d2 c0) s1 - d2 u1.
+inline void frames_loud_energy_steps(const double coef[10], FramesLoudEnergyParams *p) {
+    static_assert(kLoudRun == 16, "A^kLoudRun below is four squarings");
+    const double a1 = coef[3], a2 = coef[4], c0 = coef[5], c1 = coef[6], c2 = coef[7], d1 = coef[8], d2 = coef[9];
+    double m[16] = {-a1, 1, 0, 0, -a2, 0, 0, 0, c1 - d1 * c0, 0, -d1, 1, c2 - d2 * c0, 0, -d2, 0};
+    auto square = [](double *a) {
+        double r[16];
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) r[4 * i + j] = a[4 * i] * a[j] + a[4 * i + 1] * a[4 + j] + a[4 * i + 2] * a[8 + j] + a[4 * i + 3] * a[12 + j];
+        for (int i = 0; i < 16; ++i) a[i] = r[i];
+    };
+    for (int i = 0; i < 10; ++i) p->coef[i] = coef[i];
+    for (int k = 0; k < 4; ++k) square(m);
+    for (int k = 0; k < 8; ++k) {
+        for (int i = 0; i < 16; ++i) p->step[k][i] = m[i];
+        square(m);
+    }
+}
+
+// True peak (rc_frames_loud.hip): the 4 x oversampled rows are what FramesResampleParams defines for num / den = 1 / 4 -
+// u[c][m] = one chain acc = fmaf(table[(m % 4) * 64 + j], y[c][m / 4 - 31 + j], acc) from +0, j = 0 ... 63, y zero outside
+// [0, n) - and are never stored:
+//   norm->peak_bits = max(norm->peak_bits, bits of |v|) over every y[c][t] and u[c][m] with |v| < inf
+// by one atomicMax per workgroup that saw a non-zero one. A maximum of order-fixed chains is order-free: bit for bit.
+// `table`: the device copy of rc_resample_table(1, 4)'s 4 x 64 floats.
+struct FramesTruePeakParams {
+    const float *planar;
+    uint64_t stride;
+    uint64_t n;
+    uint32_t channels;
+    const float *table;
+    FramesNormWords *norm;
+};
+
 // (all: nothing is launched for n_frames == 0; a job of more than 2^27 frames goes out as several launches)
 hipError_t launch_frames_unpack(uint32_t format, const FramesUnpackParams &p, hipStream_t s);
 hipError_t launch_frames_pack(const FramesPackParams &p, hipStream_t s);
@@ -274,5 +370,7 @@ hipError_t launch_frames_channel_peaks(uint32_t format, const FramesChannelPeaks
 hipError_t launch_frames_resample(const FramesResampleParams &p, hipStream_t s);  // (rc_frames_resample.hip)
 hipError_t launch_frames_limit(const FramesLimitParams &p, hipStream_t s);        // (rc_frames_limit.hip)
 inline uint64_t frames_limit_scratch_words(uint64_t /*frames*/, uint32_t /*L*/) { return 0; }
+hipError_t launch_frames_loud_energy(const FramesLoudEnergyParams &p, hipStream_t s);  // (rc_frames_loud.hip)
+hipError_t launch_frames_true_peak(const FramesTruePeakParams &p, hipStream_t s);      // (rc_frames_loud.hip)
 
 }  // namespace rc

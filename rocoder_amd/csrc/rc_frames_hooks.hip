@@ -79,4 +79,21 @@ int rc_test_frames_limit(const float *src, uint64_t src0, uint64_t src_len, uint
         nullptr));
 }
 
+// (the coefficients and the matrix powers of sample_rate, as the engine forms them: frames_loud_coeffs / _energy_steps)
+int rc_test_frames_kweight_energy(const float *planar, uint64_t stride, uint64_t n, uint32_t channels, uint32_t sample_rate, uint32_t sub,
+                                  uint64_t nb, float *energy, uint64_t e_stride) {
+    rc::FramesLoudEnergyParams p{planar, stride, n, channels, sub, nb, energy, e_stride, {}, {}};
+    double coef[10];
+    rc::frames_loud_coeffs(sample_rate, coef);
+    rc::frames_loud_energy_steps(coef, &p);
+    return finish(rc::launch_frames_loud_energy(p, nullptr));
+}
+
+uint32_t rc_test_frames_loud_span(uint32_t channels, uint64_t nb) { return rc::frames_loud_span(channels, nb); }
+
+int rc_test_frames_true_peak(const float *planar, uint64_t stride, uint64_t n, uint32_t channels, const float *table,
+                             rc::FramesNormWords *norm) {
+    return finish(rc::launch_frames_true_peak(rc::FramesTruePeakParams{planar, stride, n, channels, table, norm}, nullptr));
+}
+
 }  // extern "C"

@@ -542,6 +542,48 @@ class Engine:
         self._read_limiter_stats()
         return out[:n_out]
 
+    last_lufs: Optional[float] = None       # stretch_frames_loud: the integrated loudness before the gain (np.float32, -inf: none) ...
+    last_true_peak: Optional[float] = None  # ... and the true peak before the gain (np.float32); last_gain is the gain
+
+    def stretch_frames_loud(self, frames, target_lufs: float, max_true_peak: float = 0.0, fmt: Optional[str] = None,
+                            out: Optional[np.ndarray] = None, out_fmt: str = "f32", sample_rate: int = 0) -> np.ndarray:
+        """`stretch_frames(..., out_fmt=...)` with the result loudness-normalised on the GPU in front of the quantiser
+        (rc_engine_stretch_frames_loud): the integrated loudness of BS.1770-4 / EBU R 128 (K-weighting, 400 ms blocks at
+        75 % overlap, the gates at -70 LUFS and 10 LU below, every channel at weight 1) and the 4 x oversampled true peak of
+        the whole job are measured on the device; gain = 10^((target_lufs - lufs) / 20), lowered to max_true_peak /
+        true_peak where `max_true_peak` (linear, 0: no ceiling) asks for less. `sample_rate` is the rate of the OUTPUT
+        (0: the engine's). `last_lufs`, `last_true_peak`, `last_gain` and `last_clipped` (counted after the gain) are set."""
+        with np.errstate(over="ignore"):
+            target_lufs, max_true_peak = float(np.float32(target_lufs)), float(np.float32(max_true_peak))
+        if not np.isfinite(target_lufs):
+            raise ValueError("target_lufs must be a finite float32")
+        if not max_true_peak >= 0:
+            raise ValueError("max_true_peak must be a float32 of at least 0 (0: no ceiling)")
+        if out_fmt not in _lib.PCM_FORMATS:
+            raise ValueError(f"out_fmt must be one of {sorted(_lib.PCM_FORMATS)}")
+        raw, code, n = self._raw_frames(frames, fmt)
+        n_out = self._host_output_len(n)
+        ocode = _lib.PCM_FORMATS[out_fmt]
+        dtype, tail = {"u8": (np.uint8, ()), "i16": ("<i2", ()), "i24": (np.uint8, (3,)), "i32": ("<i4", ()), "f32": ("<f4", ())}[out_fmt]
+        need = n_out * self.channels * _lib.PCM_BYTES[ocode]
+        if out is None:
+            out = np.empty(max(need, 1), np.uint8)
+        elif not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.flags.writeable and out.nbytes >= need):
+            raise ValueError(f"out must be a C-contiguous writable array of at least {need} bytes")
+        dst = out.reshape(-1).view(np.uint8)
+        got, clipped = C.c_size_t(0), C.c_uint64(0)
+        lufs, tp, gain = C.c_float(0), C.c_float(0), C.c_float(0)
+        src = C.c_void_p(raw.ctypes.data if raw.size else dst.ctypes.data)  # (no frames: any non-null pointer)
+        cap = dst.size // (self.channels * _lib.PCM_BYTES[ocode])
+        self._check(self._L.rc_engine_stretch_frames_loud(
+            self._h, src, n, code, C.c_void_p(dst.ctypes.data), cap, ocode, int(sample_rate), C.c_float(target_lufs),
+            C.c_float(max_true_peak), C.byref(got), C.byref(lufs), C.byref(tp), C.byref(gain), C.byref(clipped)))
+        assert got.value == n_out
+        self.last_lufs, self.last_true_peak, self.last_gain = np.float32(lufs.value), np.float32(tp.value), np.float32(gain.value)
+        self.last_clipped = int(clipped.value)
+        self._read_limiter_stats()
+        return dst[:need].view(dtype).reshape((n_out, self.channels) + tail)
+
     def frames_power(self, frames, fmt: Optional[str] = None, bin_frames: int = 4410) -> np.ndarray:
         """The peak of every bin of `bin_frames` whole frames of a block of interleaved PCM frames, measured on the GPU
         on the raw block (rc_engine_frames_power): float32 [ceil(n_frames / bin_frames)], the largest |x| over all
