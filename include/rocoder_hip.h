@@ -546,13 +546,31 @@ int rc_host_free(void *p);
  * `hip_stream` is a hipStream_t (NULL = the engine's own stream); the call is asynchronous
  * on that stream unless a user kernel is configured. The engine's scratch (tail copy, seam stash,
  * pipeline buffers) is per handle: a call on a different stream than the previous one first waits
- * (on the device) for that call's last enqueue, so back-to-back calls never overlap on the GPU. */
+ * (on the device) for that call's last enqueue, so back-to-back calls never overlap on the GPU.
+ *
+ * The caller's buffers (this entry, rc_engine_stretch_device_range and rc_multi_stretch_device alike; held by
+ * tests/test_gpu_caller_buffers.py on every kernel path):
+ *   - d_in and d_out need float (4-byte) alignment and no more; the result does not depend on the alignment.
+ *   - any stride of at least the row length: in_stride >= in_len, out_stride >= win_count * window_out_len (the
+ *     whole job: rc_offline_output_len). Strides may be odd; one channel ignores them.
+ *   - nothing outside [d_in + c * in_stride, + in_len) is read: hops that run past the end of a row read zeros
+ *     from the engine's own padded copy of its tail, never d_in[in_len].
+ *   - nothing outside [d_out + c * out_stride, + win_count * window_out_len) is written, whatever out_cap is.
+ * The result's bits are those of the same job in contiguous, aligned rows. */
 int rc_engine_stretch_device(rc_engine *e, const float *d_in, size_t in_stride, size_t in_len,
                              float *d_out, size_t out_stride, size_t out_cap, size_t *out_len,
                              void *hip_stream);
 /* Sharded form for multi-GPU runs: only channels [ch_first, ch_first+ch_count) and output
  * windows [win_first, win_first+win_count) of the same job; written at d_out offset 0.
- * Hops are independent given the phase source, the one-hop overlap is recomputed locally. */
+ * Hops are independent given the phase source, the one-hop overlap is recomputed locally.
+ * d_in and in_stride are the whole job's (channel c at d_in + c * in_stride, in_len its length); row i of the range is
+ * written at d_out + i * out_stride. The caller's buffers as for rc_engine_stretch_device, and of each row of the
+ * range only the span its hops cover is read - with hpw = hops_per_window and step = sample_step_len of rc_params,
+ *     [max(0, win_first * hpw - 1) * step, min(in_len, ((win_first + win_count) * hpw - 1) * step + window_len)),
+ * the hops of the range and the one in front of them (plus RC_HISTORY hops more in front where a loaded user device
+ * kernel declares a history; every channel's span where it declares RC_CROSS_CHANNEL). The rest of the rows, and the
+ * rows of channels outside the range, need not hold samples. A host frequency kernel (rc_config.kernel) carries its
+ * tail instead: no hop is recomputed. */
 int rc_engine_stretch_device_range(rc_engine *e, const float *d_in, size_t in_stride,
                                    size_t in_len, uint32_t ch_first, uint32_t ch_count,
                                    uint64_t win_first, uint64_t win_count, float *d_out,
@@ -687,7 +705,9 @@ int rc_multi_stretch_host(rc_multi *m, const float *const *in, size_t in_len, fl
 /* rc_engine_stretch_device with input and output resident on device_ids[root] (channel c at base + c * stride,
  * strides in floats): the other devices fetch the input span they need from the root and deliver their shards into
  * d_out by peer copies. `hip_stream` (a hipStream_t of the root device, or NULL) is what produced d_in: it is
- * synchronised on entry. Blocking: d_out is complete on return. */
+ * synchronised on entry. Blocking: d_out is complete on return. The caller's buffers as for rc_engine_stretch_device:
+ * float alignment, any strides of at least the row lengths (RC_EINVAL for shorter ones where there are several
+ * channels), nothing read outside the input rows, nothing written outside the first out_len floats of the output rows. */
 int rc_multi_stretch_device(rc_multi *m, uint32_t root, const float *d_in, size_t in_stride, size_t in_len,
                             float *d_out, size_t out_stride, size_t out_cap, size_t *out_len, void *hip_stream);
 /* rc_engine_load_device_kernel / _set_device_kernel_params on the engine of every listed device */
