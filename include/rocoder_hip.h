@@ -649,6 +649,32 @@ int rc_engine_resynth(rc_engine *e, uint32_t channel, uint64_t hop, const float 
  *     window, or between rounds of the processor's loop): else RC_EINVAL, and the previous kernel stays;
  *   - channels that are all closed, equally long and at the same window are computed together and need no extra analysis.
  * With these rules every entry point equals the offline job bit for bit.
+ * Whole-hop sums. A source that says `#define RC_SUMS S` in front of rc_apply (S = 1 ... RC_DK_MAX_SUMS = 4; absent or 0:
+ * none; any other value does not compile, the error names RC_SUMS) also defines
+ *   __device__ float rc_sum_term(const rc_spectrum &X, uint32_t j, const rc_hop &h, uint32_t i);   the term of sum i at bin j
+ * and rc_apply may read hop-wide quantities that are computed once per hop, not once per bin (energy, mean magnitude,
+ * centroid: what the reference's apply() forms from the whole Vec it is handed):
+ *   X.sum(i)   the sum over j = 0 ... N - 1 of rc_sum_term(X', j, h', i), where X' and h' are the hop that this rc_spectrum
+ *              stands for: X.past(d).sum(i) and X.channel(c).sum(i) are the sums of that hop of that channel, in either
+ *              order of past() and channel().
+ * Inside rc_sum_term the spectrum is that hop alone: X.past(d > 0) and X.channel(c != own) read (0, 0), X.sum(..) reads 0,
+ * h.hop and h.channel are those of the hop being summed, and h.param, h.time_ms, h.history and h.channels are as in
+ * rc_apply. A declared source without rc_sum_term does not compile (the compiler's error names rc_sum_term).
+ * Zero rules: X.sum(i) is 0.f where i >= S; where the source did not declare RC_SUMS (the call still compiles, as
+ * channel() does for an undeclared kernel); and for every spectrum that reads (0, 0) by the rules of past() and
+ * channel() - a hop before the stream, a hop beyond the declared history, a channel outside the block, the single
+ * frame's other channels - whatever rc_sum_term would return on zeros.
+ * The arithmetic is fixed: each term is a float; lane t of 256 adds the terms of bins t, t + 256, ... ascending in
+ * double; the 256 partials are combined in one fixed tree (shuffles within a wave, then the four wave partials in wave
+ * order), and the result is rounded to float once. NaN and Inf propagate as that arithmetic gives. The order depends on
+ * N alone, so the bits of a sum do not depend on the launch, chunk, range, stream batch or shard that computed it, and
+ * every entry point still equals the offline job bit for bit. (Two code objects of one source from two builds of the
+ * compiler may differ in how they round sqrtf and the like; that is outside this guarantee, which is about one code object.)
+ * S travels inside the code object (the size of its symbol rc_user_dk_sums is S + 1; the symbol is absent when S = 0),
+ * next to a second kernel, rc_user_dk_sums_pass: in front of every launch of rc_user_dk the engine runs it on the same
+ * stream, one workgroup per row of the launch's input block (the history's halo rows and, under RC_CROSS_CHANNEL, the
+ * channels analysed only included), into a scratch of rows x S floats. It reads every spectrum of the block once. A code
+ * object without the symbol takes the argument block, the launches and the scratch it always had.
  * The engine owns the prelude that defines rc_spectrum / rc_hop and the wrapper kernel rc_user_dk; rc_apply writes only
  * its return value and must terminate (a kernel cannot be preempted). Compiled with --offload-arch=gfx950 -O3 -std=c++17,
  * no fast-math. Diagnostics name rc_user_dk.hip:<line>, or the file a leading `#line 1 "name"` line names. A user device
@@ -661,7 +687,8 @@ int rc_engine_resynth(rc_engine *e, uint32_t channel, uint64_t hop, const float 
 int rc_dk_compile(const char *src, size_t src_len, char *code, size_t code_cap, size_t *code_len,
                   char *log, size_t log_cap);
 /* Loads a code object from rc_dk_compile; it runs from the next call on (code NULL: remove the kernel). The bytes are
- * checked first (ELF64, EM_AMDGPU, gfx950, an rc_user_dk symbol): RC_EINVAL, and the previous kernel stays, when they
+ * checked first (ELF64, EM_AMDGPU, gfx950, an rc_user_dk symbol, markers in range, rc_user_dk_sums_pass where sums are
+ * declared): RC_EINVAL, and the previous kernel stays, when they
  * fail; RC_EINVAL too when the engine has a host or curated kernel. A replaced module is unloaded only once every
  * launch that used it has completed, so a call already enqueued on a caller's stream finishes with the old kernel. */
 int rc_engine_load_device_kernel(rc_engine *e, const char *code, size_t code_len);

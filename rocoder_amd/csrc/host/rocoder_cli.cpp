@@ -763,8 +763,9 @@ static const DkApi &dk_api() {
 
 // The history depth a code object declares (RC_HISTORY in its source): the size of its ELF symbol rc_user_dk_history
 // less one, 0 without the symbol. The watcher hands over bytes only, so the log line reads it from them. With `cross`:
-// whether the object declares RC_CROSS_CHANNEL (defines the symbol rc_user_dk_channels) instead.
-static unsigned dk_history_of(const std::string &code, bool cross = false) {
+// whether the object declares RC_CROSS_CHANNEL (defines the symbol rc_user_dk_channels) instead. With `sums`: the RC_SUMS
+// it declares, the size of the symbol rc_user_dk_sums less one, instead.
+static unsigned dk_history_of(const std::string &code, bool cross = false, bool sums = false) {
     const unsigned char *p = (const unsigned char *)code.data();
     const size_t len = code.size();
     auto rd = [&](uint64_t off, size_t n) -> uint64_t {
@@ -773,7 +774,9 @@ static unsigned dk_history_of(const std::string &code, bool cross = false) {
         for (size_t i = 0; i < n; ++i) x |= (uint64_t)p[off + i] << (8 * i);
         return x;
     };
-    static const char kHist[] = "rc_user_dk_history", kChan[] = "rc_user_dk_channels";
+    static const char kHistory[] = "rc_user_dk_history", kChan[] = "rc_user_dk_channels", kSums[] = "rc_user_dk_sums";
+    const char *const kHist = sums ? kSums : kHistory;
+    const size_t kHistLen = sums ? sizeof kSums : sizeof kHistory;
     if (len < 64 || memcmp(p, "\x7f" "ELF", 4) != 0 || p[4] != 2 || p[5] != 1) return 0;
     const uint64_t shoff = rd(40, 8), shnum = rd(60, 2);
     if (rd(58, 2) != 64 || shoff > len || shnum > (len - shoff) / 64) return 0;
@@ -790,7 +793,7 @@ static unsigned dk_history_of(const std::string &code, bool cross = false) {
                     return 1;
                 continue;
             }
-            if (name < str_size && str_size - name >= sizeof kHist && memcmp(p + str_off + name, kHist, sizeof kHist) == 0) {
+            if (name < str_size && str_size - name >= kHistLen && memcmp(p + str_off + name, kHist, kHistLen) == 0) {
                 const uint64_t sz = rd(sym + 16, 8);
                 return sz >= 1 ? (unsigned)(sz - 1) : 0;
             }
@@ -889,9 +892,12 @@ struct Engine {
         if (!code) return;
         const bool cross = dk_history_of(*code, true) != 0;
         const int rc = dk_api().load(h, code->data(), code->size());
-        if (rc == RC_OK)
-            fprintf(stderr, "INFO Got new device kernel (history: %u earlier hops%s)\n", dk_history_of(*code),
-                    cross ? ", reads the other channels" : "");
+        if (rc == RC_OK) {
+            const unsigned n_sums = dk_history_of(*code, false, true);
+            const std::string sums = n_sums ? ", " + std::to_string(n_sums) + " whole-hop sums" : std::string();
+            fprintf(stderr, "INFO Got new device kernel (history: %u earlier hops%s%s)\n", dk_history_of(*code),
+                    cross ? ", reads the other channels" : "", sums.c_str());
+        }
         else if (rc == RC_EINVAL && cross)
             dk_held = std::move(code);
         else
@@ -1218,6 +1224,7 @@ void usage() {
             "                                       __device__ float2 rc_apply(const rc_spectrum &X, uint32_t j, const rc_hop &h)\n"
             "                                       A source that says #define RC_HISTORY D (D <= 8) also reads X.past(1..D), the D hops before\n"
             "                                       One that says #define RC_CROSS_CHANNEL 1 also reads X.channel(c), the other channels' spectra\n"
+            "                                       One that says #define RC_SUMS S (S <= 4) and defines rc_sum_term(X, j, h, i) also reads X.sum(i), sums over the whole hop\n"
             "        --dk-params <a,b,...>          Up to 16 floats for --device-kernel-src (h.param(i))\n"
             "        --kernel-threads <n>           Host threads calling --freq-kernel (channels in parallel; needs a re-entrant kernel)\n"
             "        --seed <u64>                   Phase-source seed (the reference uses an unseeded thread_rng)\n"

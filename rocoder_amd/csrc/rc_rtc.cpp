@@ -160,7 +160,8 @@ int rtc_compile(const char *src, size_t src_len, std::string *code, std::string 
     return rc;
 }
 
-int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32_t *history, bool *cross) {
+int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32_t *history, bool *cross,
+                          uint32_t *sums) {
     const unsigned char *p = (const unsigned char *)code;
     uint64_t v = 0;
     if (!p || len < 64 || std::memcmp(p, "\x7f" "ELF", 4) != 0 || p[4] != 2 /* ELFCLASS64 */ || p[5] != 1 /* LE */) {
@@ -186,8 +187,10 @@ int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32
         return RC_EINVAL;
     }
     static const char kSym[] = "rc_user_dk", kHist[] = "rc_user_dk_history", kChan[] = "rc_user_dk_channels";
-    bool found = false, chan = false;
+    static const char kSums[] = "rc_user_dk_sums", kPass[] = "rc_user_dk_sums_pass";
+    bool found = false, chan = false, sums_marker = false, pass = false;
     uint64_t hist_size = 1;  // no marker: depth 0
+    uint64_t sums_size = 1;  // no marker: no sums
     for (uint64_t i = 0; i < shnum; ++i) {
         const uint64_t sh = shoff + i * 64;
         uint64_t type = 0, off = 0, size = 0, link = 0, entsize = 0;
@@ -210,6 +213,11 @@ int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32
             if (str_size - name >= sizeof kHist && std::memcmp(p + str_off + name, kHist, sizeof kHist) == 0)
                 rd(p, len, s + 16, 8, &hist_size);  // st_size
             if (str_size - name >= sizeof kChan && std::memcmp(p + str_off + name, kChan, sizeof kChan) == 0) chan = true;
+            if (str_size - name >= sizeof kSums && std::memcmp(p + str_off + name, kSums, sizeof kSums) == 0) {
+                sums_marker = true;
+                rd(p, len, s + 16, 8, &sums_size);
+            }
+            if (str_size - name >= sizeof kPass && std::memcmp(p + str_off + name, kPass, sizeof kPass) == 0) pass = true;
         }
     }
     if (!found) {
@@ -220,29 +228,43 @@ int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32
         *why = "the code object declares an RC_HISTORY outside 0 ... " + std::to_string(DK_MAX_HISTORY);
         return RC_EINVAL;
     }
+    if (sums_marker && (sums_size < 1 || sums_size > DK_MAX_SUMS + 1)) {
+        *why = "the code object declares an RC_SUMS outside 0 ... " + std::to_string(DK_MAX_SUMS);
+        return RC_EINVAL;
+    }
+    if (sums_marker && !pass) {
+        *why = "the code object declares RC_SUMS and defines no rc_user_dk_sums_pass kernel";
+        return RC_EINVAL;
+    }
     if (history) *history = (uint32_t)(hist_size - 1);
     if (cross) *cross = chan;
+    if (sums) *sums = (uint32_t)(sums_size - 1);
     return RC_OK;
 }
 
 struct UserModule {
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
+    hipFunction_t fn_sums = nullptr;  // rc_user_dk_sums_pass, with sums > 0 only
     uint32_t history = 0;
     bool cross = false;
+    uint32_t sums = 0;
 };
 
 int rtc_load(const void *code, size_t len, UserModule **out, std::string *why) {
     *out = nullptr;
     uint32_t history = 0;
     bool cross = false;
-    if (int rc = rtc_check_code_object(code, len, why, &history, &cross)) return rc;
+    uint32_t sums = 0;
+    if (int rc = rtc_check_code_object(code, len, why, &history, &cross, &sums)) return rc;
     UserModule *m = new UserModule;
     m->history = history;
     m->cross = cross;
+    m->sums = sums;
     hipError_t e = hipModuleLoadData(&m->mod, code);
     if (e == hipSuccess) {
         e = hipModuleGetFunction(&m->fn, m->mod, "rc_user_dk");
+        if (e == hipSuccess && sums) e = hipModuleGetFunction(&m->fn_sums, m->mod, "rc_user_dk_sums_pass");
         if (e != hipSuccess) (void)hipModuleUnload(m->mod);
     }
     if (e != hipSuccess) {
@@ -263,6 +285,7 @@ void rtc_unload(UserModule *m) {
 
 uint32_t rtc_history(const UserModule *m) { return m ? m->history : 0; }
 bool rtc_cross(const UserModule *m) { return m && m->cross; }
+uint32_t rtc_sums(const UserModule *m) { return m ? m->sums : 0; }
 
 hipError_t rtc_launch(const UserModule *m, UserDkArgs a, uint64_t rows, hipStream_t s) {
     const uint64_t per_launch = 32768;  // grid.y limit, as launch_dev_kernel
@@ -271,6 +294,19 @@ hipError_t rtc_launch(const UserModule *m, UserDkArgs a, uint64_t rows, hipStrea
         const unsigned gy = (unsigned)(rows - r0 < per_launch ? rows - r0 : per_launch);
         void *args[] = {&a};
         const hipError_t e = hipModuleLaunchKernel(m->fn, (a.n + 255) / 256, gy, 1, 256, 1, 1, 0, s, args, nullptr);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t rtc_launch_sums(const UserModule *m, UserDkArgs a, uint64_t rows, hipStream_t s) {
+    if (!m->fn_sums) return hipErrorInvalidDeviceFunction;
+    const uint64_t per_launch = 32768;  // grid.y limit, as rtc_launch
+    for (uint64_t r0 = 0; r0 < rows; r0 += per_launch) {
+        a.row_first = r0;
+        const unsigned gy = (unsigned)(rows - r0 < per_launch ? rows - r0 : per_launch);
+        void *args[] = {&a};
+        const hipError_t e = hipModuleLaunchKernel(m->fn_sums, 1, gy, 1, 256, 1, 1, 0, s, args, nullptr);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -11,6 +11,7 @@
 namespace rc {
 
 constexpr uint32_t DK_MAX_PARAMS = 16;
+constexpr uint32_t DK_MAX_SUMS = 4;     // RC_DK_MAX_SUMS: whole-hop sums a user device kernel may declare (an interface constant)
 constexpr uint32_t DK_MAX_HISTORY = 8;  // RC_DK_MAX_HISTORY: earlier hops a user device kernel may read (an interface constant)
 
 // Host mirror of the prelude's rc_dk_args (the wrapper kernel's one argument): keep the two in step
@@ -35,8 +36,14 @@ struct UserDkArgs {
     uint32_t in_ch_first;
     uint32_t in_ch_count;
     uint32_t pad2_;
+    // rc_dk_args_sums: what a kernel that declares RC_SUMS takes on top, whatever else it declares: the sums of the
+    // rows of `in`, [in_ch_count][halo + hop_count][n_sums], pointing past the first channel's halo rows as `in` does
+    const float *sums;
+    uint32_t n_sums;
+    uint32_t pad3_;
 };
-static_assert(offsetof(UserDkArgs, in_rows) == 128 && offsetof(UserDkArgs, channels) == 144 && sizeof(UserDkArgs) == 160,
+static_assert(offsetof(UserDkArgs, in_rows) == 128 && offsetof(UserDkArgs, channels) == 144 &&
+                  offsetof(UserDkArgs, sums) == 160 && sizeof(UserDkArgs) == 176,
               "rc_dk_args layout");
 
 // Every function returns an RC_* status and, on failure, a one-line reason in *why.
@@ -50,17 +57,24 @@ int rtc_compile(const char *src, size_t src_len, std::string *code, std::string 
 // *history (when given): the depth the object declares, the size of its symbol rc_user_dk_history less one; 0 for an
 // object without that symbol. A size outside 1 ... DK_MAX_HISTORY + 1 is RC_EINVAL. Reads nothing outside
 // [code, code + len). *cross (when given): whether the object declares RC_CROSS_CHANNEL, i.e. defines the symbol
-// rc_user_dk_channels.
+// rc_user_dk_channels. *sums (when given): the RC_SUMS the object declares, the size of its symbol rc_user_dk_sums less
+// one; 0 for an object without that symbol. A size outside 1 ... DK_MAX_SUMS + 1, and a marker without the symbol
+// rc_user_dk_sums_pass, is RC_EINVAL.
 int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32_t *history = nullptr,
-                          bool *cross = nullptr);
+                          bool *cross = nullptr, uint32_t *sums = nullptr);
 
 struct UserModule;
-// hipModuleLoadData + hipModuleGetFunction("rc_user_dk") on the current device (RC_EHIP on failure)
+// hipModuleLoadData + hipModuleGetFunction("rc_user_dk") on the current device (RC_EHIP on failure); an object that
+// declares RC_SUMS is asked for "rc_user_dk_sums_pass" as well, any other for nothing more
 int rtc_load(const void *code, size_t len, UserModule **out, std::string *why);
 void rtc_unload(UserModule *m);
 uint32_t rtc_history(const UserModule *m);  // the depth the loaded object declares
 bool rtc_cross(const UserModule *m);        // whether it declares RC_CROSS_CHANNEL
+uint32_t rtc_sums(const UserModule *m);     // the RC_SUMS it declares
 // rows = hop spectra of a.n bins to write; a.row_first is set per launch (rows are chunked below the grid.y limit)
 hipError_t rtc_launch(const UserModule *m, UserDkArgs a, uint64_t rows, hipStream_t s);
+// rc_user_dk_sums_pass of a module that declares RC_SUMS: one workgroup per row of the INPUT block, rows =
+// a.in_ch_count * a.in_rows (halo rows included), chunked in the same way
+hipError_t rtc_launch_sums(const UserModule *m, UserDkArgs a, uint64_t rows, hipStream_t s);
 
 }  // namespace rc

@@ -18,6 +18,22 @@
 // channel, where the source did not declare RC_CROSS_CHANNEL. h.channels is rc_config::channels under the declaration and
 // 0 without it: the 128-byte argument block of an undeclared kernel is unchanged and has no room for it. The wrapper
 // records the declaration as the symbol rc_user_dk_channels, which the loader looks for.
+//
+// A source that says `#define RC_SUMS S` (1 ... RC_DK_MAX_SUMS; absent or 0: none) also writes
+//   __device__ float rc_sum_term(const rc_spectrum &X, uint32_t j, const rc_hop &h, uint32_t i);   // the term of sum i at bin j
+// and rc_apply may read X.sum(i), the sum over j = 0 ... N - 1 of rc_sum_term(X', j, h', i), where X' and h' are the hop
+// that this rc_spectrum stands for: X.past(d).sum(i) and X.channel(c).sum(i) are the sums of that hop of that channel,
+// in either order of past() and channel(). Inside rc_sum_term the spectrum is that hop alone: X.past(d > 0) and
+// X.channel(c != own) read (0, 0), X.sum(..) reads 0, h.hop and h.channel are those of the hop being summed, and
+// h.param, h.time_ms, h.history and h.channels are as in rc_apply. Zero rules: X.sum(i) is 0.f where i >= S, where the
+// source did not declare RC_SUMS (the call still compiles), and for every spectrum that reads (0, 0) by the rules of
+// past() and channel() - a hop before the stream or beyond the declared history, a channel outside the block, a single
+// frame's other channels - whatever rc_sum_term would return on zeros. The arithmetic: each term is a float; lane t of
+// 256 adds the terms of bins t, t + 256, ... ascending in double; the 256 partials are combined in one fixed tree
+// (shuffles within a wave, then the four wave partials in wave order) and the result is rounded to float once. NaN and
+// Inf propagate as that arithmetic gives. The order depends on N alone, so the bits of a sum do not depend on the launch,
+// chunk, range, stream batch or shard that computed it. The wrapper records S in the code object as the size of the
+// symbol rc_user_dk_sums (S + 1 bytes, present only when S > 0), and adds the kernel rc_user_dk_sums_pass.
 R"rc_prelude(
 typedef __hip_internal::uint32_t uint32_t;
 typedef __hip_internal::int32_t int32_t;
@@ -60,6 +76,7 @@ struct rc_spectrum {
             s.past_ = 0;
         } else {
             s.p_ = p_ - (uint64_t)d * n;
+            s.sums_ = sums_ - (uint64_t)d * n_sums_;
             s.past_ = past_ - d;
         }
         return s;
@@ -72,15 +89,21 @@ struct rc_spectrum {
             s.zero_ = true;
         } else {
             s.p_ = p_ + ((int64_t)c - (int64_t)ch_) * (int64_t)((uint64_t)ch_rows_ * n);
+            s.sums_ = sums_ + ((int64_t)c - (int64_t)ch_) * (int64_t)((uint64_t)ch_rows_ * n_sums_);
             s.ch_ = c;
         }
         return s;
     }
+    // sum i of this hop (RC_SUMS, rc_sum_term): 0.f where i >= RC_SUMS, without the declaration, and where this
+    // spectrum reads (0, 0)
+    __device__ float sum(uint32_t i) const { return (zero_ || i >= n_sums_) ? 0.f : sums_[i]; }
     uint32_t past_;  // rows in front of p_ that past() may reach
     bool zero_;      // a hop outside the declared history or before the stream, a channel outside the block: (0, 0)
     uint32_t ch_;            // the channel p_ belongs to
     uint32_t ch_lo_, ch_n_;  // channels [ch_lo_, ch_lo_ + ch_n_) lie in the block (undeclared: none but ch_)
     uint32_t ch_rows_;       // rows from one channel of the block to the next
+    const float *sums_;      // the n_sums_ sums of the row p_ (rows of sums lie as the rows of spectra do)
+    uint32_t n_sums_;        // the declared RC_SUMS; 0 without it and inside rc_sum_term
 };
 
 // What the hop is: window length, channel, hop index k (the k of rc_phase_key), the launch's time and the params.
@@ -115,5 +138,16 @@ struct rc_dk_args_channels : rc_dk_args_history {
     uint32_t in_ch_first;  // first channel of the input block
     uint32_t in_ch_count;  // channels in the input block (a single frame: 1, its own)
     uint32_t pad2_;
+};
+
+#define RC_DK_MAX_SUMS 4
+
+// the argument block of a kernel that declares RC_SUMS, whatever else it declares (the host fills every field above for
+// every kernel): `sums` is row 0 of [in_ch_count channels][halo + hop_count][RC_SUMS] past the first channel's halo rows,
+// parallel to the rows of `in`. rc_user_dk_sums_pass writes it, rc_user_dk reads it. Host mirror: rc::UserDkArgs.
+struct rc_dk_args_sums : rc_dk_args_channels {
+    const float *sums;
+    uint32_t n_sums;  // RC_SUMS
+    uint32_t pad3_;
 };
 )rc_prelude"

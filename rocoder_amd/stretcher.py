@@ -124,6 +124,16 @@ def device_kernel_cross_channel(code: bytes) -> bool:
     return any(name == b"rc_user_dk_channels" for name, _size in _code_object_symbols(code))
 
 
+def device_kernel_sums(code: bytes) -> int:
+    """The number of whole-hop sums a code object from compile_device_kernel declares (`#define RC_SUMS S` in its source:
+    rc_apply reads X.sum(0..S-1), the sums of rc_sum_term over a hop's bins), 0 for a source without them. Pure Python:
+    S is the size of the ELF symbol rc_user_dk_sums less one, and a code object without that symbol has none."""
+    for name, size in _code_object_symbols(code):
+        if name == b"rc_user_dk_sums":
+            return max(0, size - 1)
+    return 0
+
+
 def device_kernel_history(code: bytes) -> int:
     """The history depth a code object from compile_device_kernel declares (`#define RC_HISTORY D` in its source: the
     earlier hops X.past(1..D) that rc_apply reads), 0 for a source without one. Pure Python: the depth is the size of
