@@ -618,7 +618,7 @@ int rc_engine_resynth(rc_engine *e, uint32_t channel, uint64_t hop, const float 
  *              stream (src/stretcher.rs:58-59), and a stateful kernel has seen no call before hop 0.
  *   h.history  the declared D
  * No d and no index leaves the launch's spectrum block. A larger D does not compile (the error names RC_HISTORY). Earlier
- * OUTPUTS (feedback) cannot be read. The depth travels inside the code object (the size of its symbol
+ * OUTPUTS are read through X.out(d) (Feedback, below). The depth travels inside the code object (the size of its symbol
  * rc_user_dk_history is D + 1), so loading needs no further argument; a code object without that symbol runs as D = 0.
  * Every range, streaming batch and rc_multi shard recomputes the D spectra in front of it from the input, so all entry
  * points equal the offline job; an open stream retains RC_DK_MAX_HISTORY + 1 steps of input behind its next hop, so
@@ -675,6 +675,43 @@ int rc_engine_resynth(rc_engine *e, uint32_t channel, uint64_t hop, const float 
  * stream, one workgroup per row of the launch's input block (the history's halo rows and, under RC_CROSS_CHANNEL, the
  * channels analysed only included), into a scratch of rows x S floats. It reads every spectrum of the block once. A code
  * object without the symbol takes the argument block, the launches and the scratch it always had.
+ * Feedback. A source that says `#define RC_FEEDBACK F` in front of rc_apply (F = 1 ... RC_DK_MAX_FEEDBACK = 4; absent or 0:
+ * none; any other value does not compile, the error names RC_FEEDBACK) may also read its own earlier OUTPUTS, the static
+ * state a reference apply() keeps between calls (peak hold with a release, freeze, one-pole smoothing, feedback delays):
+ *   X.out(d)    the spectrum rc_apply returned for hop h.hop - d of the same channel, an rc_spectrum (read-only, the same
+ *               modulo-N indexing)
+ *   h.feedback  the declared F
+ * X.out(d) reads (0, 0) where d == 0; where d > F; where h.hop - d < 0; where hop h.hop - d lies before the first hop this
+ * kernel ran since it was loaded, or since its channel last restarted at hop 0 (a freshly swapped-in reference library
+ * starts from fresh statics); where the source did not declare RC_FEEDBACK (the call still compiles); in
+ * rc_engine_resynth (a single frame); inside rc_sum_term; and for X.channel(c).out(d) and X.past(p).out(d) with c another
+ * channel or p > 0: out() belongs to rc_apply's own X. An out spectrum is bins only: its past(), channel() and out() read
+ * (0, 0) and its sum() reads 0. X.out(d) composes with RC_HISTORY, RC_CROSS_CHANNEL and RC_SUMS on X itself.
+ * Such a kernel is SEQUENTIAL, as rc_config::kernel is: the hops of a channel run in order, once each. Per channel, a call
+ * that starts at hop k0 is one of
+ *   - a restart, k0 == 0: the state and the overlap tail are zeroed;
+ *   - a continuation, k0 == the hop behind the channel's previous call: the overlap tail is carried on the device, hop
+ *     k0 - 1 is not computed again;
+ *   - the first call since the kernel was loaded, k0 > 0 (a hot swap into a running stream): the state is zeroed and hop
+ *     k0 - 1 runs once for its overlap tail, as the hop in front of every range start does. It sees zero state, and its
+ *     output enters the state: it is X.out(1) of hop k0;
+ *   - anything else: RC_EINVAL, the message names the hop expected, state and tail stay as they were, and the in-order
+ *     call still succeeds afterwards.
+ * A call whose channels fall into different cases is RC_EINVAL. A call that fails after it began leaves only a restart at
+ * hop 0 acceptable, as for a host kernel. The whole-job entries start at hop 0 and run their chunks in order; consecutive
+ * rc_engine_stretch_device_range calls and the streaming seam (open or closed, look-ahead batches included; the channels
+ * may stand at different windows) continue. rc_multi_load_device_kernel returns RC_EUNSUPPORTED for such a kernel and
+ * keeps the one it runs: a job cut over devices cannot promise the order. With these rules every entry point equals the
+ * offline job bit for bit.
+ * F travels inside the code object (the size of its symbol rc_user_dk_feedback is F + 1; the symbol is absent when F = 0;
+ * a size outside 2 ... 5 is refused). The state, rc_config::channels x (F + 1) rows of N float2 in device memory (row =
+ * hop mod (F + 1), so that no hop writes a row it may read), is reserved by rc_engine_load_device_kernel - RC_ENOMEM
+ * there, not mid-job - and freed with the module. The kernel writes every Y[j] to the spectrum block, as any user kernel
+ * does, and to its ring row. Nothing waits on the device: the hops of a chunk are one launch each, ordered by the stream,
+ * or, at N <= 1024, one launch of one workgroup per channel that walks the chunk's hops with a barrier between them. Both
+ * give the same bits. A feedback kernel is therefore bound by one launch, or one barrier round, per hop (DESIGN 6,
+ * "Feedback", has the measured cost); rc_engine_last_kernel_stats counts the launches made. A code object without the
+ * symbol takes the argument block, the launches and the scratch it always had.
  * The engine owns the prelude that defines rc_spectrum / rc_hop and the wrapper kernel rc_user_dk; rc_apply writes only
  * its return value and must terminate (a kernel cannot be preempted). Compiled with --offload-arch=gfx950 -O3 -std=c++17,
  * no fast-math. Diagnostics name rc_user_dk.hip:<line>, or the file a leading `#line 1 "name"` line names. A user device
@@ -689,7 +726,8 @@ int rc_dk_compile(const char *src, size_t src_len, char *code, size_t code_cap, 
 /* Loads a code object from rc_dk_compile; it runs from the next call on (code NULL: remove the kernel). The bytes are
  * checked first (ELF64, EM_AMDGPU, gfx950, an rc_user_dk symbol, markers in range, rc_user_dk_sums_pass where sums are
  * declared): RC_EINVAL, and the previous kernel stays, when they
- * fail; RC_EINVAL too when the engine has a host or curated kernel. A replaced module is unloaded only once every
+ * fail; RC_EINVAL too when the engine has a host or curated kernel; RC_ENOMEM, and the previous kernel stays, when the
+ * state of a kernel that declares RC_FEEDBACK cannot be reserved. A replaced module is unloaded only once every
  * launch that used it has completed, so a call already enqueued on a caller's stream finishes with the old kernel. */
 int rc_engine_load_device_kernel(rc_engine *e, const char *code, size_t code_len);
 /* Up to 16 float params (h.param(i)), passed by value with every launch: they take effect from the next call, with no
@@ -704,7 +742,8 @@ int rc_engine_set_device_kernel_params(rc_engine *e, const float *params, uint32
  * recomputed locally, no data-path collective), and every shard's output copied ONCE, straight into its place in the
  * caller's layout (device form: hipMemcpyPeerAsync into the root device's tensor; host form: device -> the caller's
  * arrays). A host frequency kernel (rc_config::kernel) is RC_EUNSUPPORTED here: a stateful apply() sees its
- * channel's hops in order, which a cut job cannot promise; the curated and user device kernels work. rc_config::device is
+ * channel's hops in order, which a cut job cannot promise; the curated and user device kernels work, except a user
+ * device kernel that declares RC_FEEDBACK (rc_multi_load_device_kernel: RC_EUNSUPPORTED, for the same reason). rc_config::device is
  * ignored. A device may be listed more than once (then its engines share it). Threading as for an engine: one thread
  * at a time per rc_multi handle; the handle owns one persistent worker thread per listed device beyond the first (created
  * by rc_multi_create, joined by rc_multi_destroy), and the calling thread's current HIP device is restored on return. */

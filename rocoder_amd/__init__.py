@@ -3,7 +3,8 @@ overlap-add stretch path. The compute lives in librocoder_hip.so (hand-written H
 include/rocoder_hip.h); this package is the host-side mirror of the reference interface."""
 from .stretcher import (AudioBus, AudioSpec, DeviceKernelCompileError, Engine, MultiEngine, ReFFT,  # noqa: F401
                         RocoderError, Stretcher, StretcherProcessor, autocrop_points, compile_device_kernel, derive_params,
-                        device_kernel_cross_channel, device_kernel_history, device_kernel_sums, load_kernel_library,
+                        device_kernel_cross_channel, device_kernel_feedback, device_kernel_history, device_kernel_sums,
+                        load_kernel_library,
                         offline_output_len, pinned_empty, split_mono_map, stretch)
 
 __version__ = "0.1.0"

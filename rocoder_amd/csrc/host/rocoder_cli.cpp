@@ -764,8 +764,9 @@ static const DkApi &dk_api() {
 // The history depth a code object declares (RC_HISTORY in its source): the size of its ELF symbol rc_user_dk_history
 // less one, 0 without the symbol. The watcher hands over bytes only, so the log line reads it from them. With `cross`:
 // whether the object declares RC_CROSS_CHANNEL (defines the symbol rc_user_dk_channels) instead. With `sums`: the RC_SUMS
-// it declares, the size of the symbol rc_user_dk_sums less one, instead.
-static unsigned dk_history_of(const std::string &code, bool cross = false, bool sums = false) {
+// it declares, the size of the symbol rc_user_dk_sums less one, instead. With `feedback`: the RC_FEEDBACK it declares, the
+// size of the symbol rc_user_dk_feedback less one, instead.
+static unsigned dk_history_of(const std::string &code, bool cross = false, bool sums = false, bool feedback = false) {
     const unsigned char *p = (const unsigned char *)code.data();
     const size_t len = code.size();
     auto rd = [&](uint64_t off, size_t n) -> uint64_t {
@@ -775,8 +776,9 @@ static unsigned dk_history_of(const std::string &code, bool cross = false, bool 
         return x;
     };
     static const char kHistory[] = "rc_user_dk_history", kChan[] = "rc_user_dk_channels", kSums[] = "rc_user_dk_sums";
-    const char *const kHist = sums ? kSums : kHistory;
-    const size_t kHistLen = sums ? sizeof kSums : sizeof kHistory;
+    static const char kFeedback[] = "rc_user_dk_feedback";
+    const char *const kHist = feedback ? kFeedback : sums ? kSums : kHistory;
+    const size_t kHistLen = feedback ? sizeof kFeedback : sums ? sizeof kSums : sizeof kHistory;
     if (len < 64 || memcmp(p, "\x7f" "ELF", 4) != 0 || p[4] != 2 || p[5] != 1) return 0;
     const uint64_t shoff = rd(40, 8), shnum = rd(60, 2);
     if (rd(58, 2) != 64 || shoff > len || shnum > (len - shoff) / 64) return 0;
@@ -894,7 +896,8 @@ struct Engine {
         const int rc = dk_api().load(h, code->data(), code->size());
         if (rc == RC_OK) {
             const unsigned n_sums = dk_history_of(*code, false, true);
-            const std::string sums = n_sums ? ", " + std::to_string(n_sums) + " whole-hop sums" : std::string();
+            std::string sums = n_sums ? ", " + std::to_string(n_sums) + " whole-hop sums" : std::string();
+            if (const unsigned n_fb = dk_history_of(*code, false, false, true)) sums += ", " + std::to_string(n_fb) + " earlier outputs";
             fprintf(stderr, "INFO Got new device kernel (history: %u earlier hops%s%s)\n", dk_history_of(*code),
                     cross ? ", reads the other channels" : "", sums.c_str());
         }
@@ -1225,6 +1228,7 @@ void usage() {
             "                                       A source that says #define RC_HISTORY D (D <= 8) also reads X.past(1..D), the D hops before\n"
             "                                       One that says #define RC_CROSS_CHANNEL 1 also reads X.channel(c), the other channels' spectra\n"
             "                                       One that says #define RC_SUMS S (S <= 4) and defines rc_sum_term(X, j, h, i) also reads X.sum(i), sums over the whole hop\n"
+            "                                       One that says #define RC_FEEDBACK F (F <= 4) also reads X.out(1..F), what it returned for the F hops before\n"
             "        --dk-params <a,b,...>          Up to 16 floats for --device-kernel-src (h.param(i))\n"
             "        --kernel-threads <n>           Host threads calling --freq-kernel (channels in parallel; needs a re-entrant kernel)\n"
             "        --seed <u64>                   Phase-source seed (the reference uses an unseeded thread_rng)\n"

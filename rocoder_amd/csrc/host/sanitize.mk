@@ -7,7 +7,7 @@
 ROOT := ../../..
 CXX  ?= g++
 COMMON := -g -O1 -std=c++17 -Wall -fno-omit-frame-pointer rocoder_cli.cpp -ldl -lpthread
-all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../bin/engine_tsan ../../bin/engine_dk_asan ../../bin/engine_xch_asan ../../bin/engine_frames_asan ../../bin/engine_frames_pcm_asan ../../bin/engine_frames_norm_asan ../../bin/engine_frames_fade_asan ../../bin/engine_frames_power_asan ../../bin/engine_frames_map_asan ../../bin/engine_frames_dither_asan ../../bin/engine_frames_resample_asan ../../bin/engine_frames_limit_asan ../../bin/engine_frames_loud_asan ../../bin/engine_dk_sums_asan
+all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../bin/engine_tsan ../../bin/engine_dk_asan ../../bin/engine_xch_asan ../../bin/engine_frames_asan ../../bin/engine_frames_pcm_asan ../../bin/engine_frames_norm_asan ../../bin/engine_frames_fade_asan ../../bin/engine_frames_power_asan ../../bin/engine_frames_map_asan ../../bin/engine_frames_dither_asan ../../bin/engine_frames_resample_asan ../../bin/engine_frames_limit_asan ../../bin/engine_frames_loud_asan ../../bin/engine_dk_sums_asan ../../bin/engine_dk_fb_asan
 ../../bin/rocoder_asan: rocoder_cli.cpp $(ROOT)/include/rocoder_hip.h ../../librocoder_hip.so
 	mkdir -p ../../bin
 	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(COMMON) -o $@ -L../.. -lrocoder_hip \
@@ -73,6 +73,12 @@ ENGINE_SUMS_ASAN_OBJ := $(filter-out ../../bin/hip_stub_rtc.asan.o,$(ENGINE_ASAN
 ../../bin/hip_stub_rtc_sums.asan.o: $(ROOT)/tests/c/hip_stub_rtc_sums.h
 ../../bin/engine_dk_sums_asan: $(ROOT)/tests/c/engine_host_driver_dk_sums.cpp $(ENGINE_SUMS_ASAN_OBJ) $(ENGINE_HDR) $(ROOT)/tests/c/hip_stub_rtc_sums.h
 	$(CXX) $(ASAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_SUMS_ASAN_OBJ) -o $@ -lpthread -ldl
+#   dk_fb        a user device kernel that reads its earlier outputs loaded, over hip_stub_rtc_fb.cpp in place of
+#                hip_stub_rtc.cpp (it logs every lookup and launch and walks the ring rows of every launch)
+ENGINE_FB_ASAN_OBJ := $(filter-out ../../bin/hip_stub_rtc.asan.o,$(ENGINE_ASAN_OBJ)) ../../bin/hip_stub_rtc_fb.asan.o
+../../bin/hip_stub_rtc_fb.asan.o: $(ROOT)/tests/c/hip_stub_rtc_fb.h
+../../bin/engine_dk_fb_asan: $(ROOT)/tests/c/engine_host_driver_dk_fb.cpp $(ENGINE_FB_ASAN_OBJ) $(ENGINE_HDR) $(ROOT)/tests/c/hip_stub_rtc_fb.h
+	$(CXX) $(ASAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_FB_ASAN_OBJ) -o $@ -lpthread -ldl
 ../../bin/engine_%_asan: $(ROOT)/tests/c/engine_host_driver_%.cpp $(ENGINE_ASAN_OBJ) $(ENGINE_HDR)
 	$(CXX) $(ASAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_ASAN_OBJ) -o $@ -lpthread -ldl
 ../../bin/engine_%_tsan: $(ROOT)/tests/c/engine_host_driver_%.cpp $(ENGINE_TSAN_OBJ) $(ENGINE_HDR)

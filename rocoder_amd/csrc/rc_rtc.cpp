@@ -161,7 +161,7 @@ int rtc_compile(const char *src, size_t src_len, std::string *code, std::string 
 }
 
 int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32_t *history, bool *cross,
-                          uint32_t *sums) {
+                          uint32_t *sums, uint32_t *feedback) {
     const unsigned char *p = (const unsigned char *)code;
     uint64_t v = 0;
     if (!p || len < 64 || std::memcmp(p, "\x7f" "ELF", 4) != 0 || p[4] != 2 /* ELFCLASS64 */ || p[5] != 1 /* LE */) {
@@ -188,7 +188,9 @@ int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32
     }
     static const char kSym[] = "rc_user_dk", kHist[] = "rc_user_dk_history", kChan[] = "rc_user_dk_channels";
     static const char kSums[] = "rc_user_dk_sums", kPass[] = "rc_user_dk_sums_pass";
-    bool found = false, chan = false, sums_marker = false, pass = false;
+    static const char kFb[] = "rc_user_dk_feedback";
+    bool found = false, chan = false, sums_marker = false, pass = false, fb_marker = false;
+    uint64_t fb_size = 1;  // no marker: no feedback
     uint64_t hist_size = 1;  // no marker: depth 0
     uint64_t sums_size = 1;  // no marker: no sums
     for (uint64_t i = 0; i < shnum; ++i) {
@@ -218,6 +220,10 @@ int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32
                 rd(p, len, s + 16, 8, &sums_size);
             }
             if (str_size - name >= sizeof kPass && std::memcmp(p + str_off + name, kPass, sizeof kPass) == 0) pass = true;
+            if (str_size - name >= sizeof kFb && std::memcmp(p + str_off + name, kFb, sizeof kFb) == 0) {
+                fb_marker = true;
+                rd(p, len, s + 16, 8, &fb_size);
+            }
         }
     }
     if (!found) {
@@ -236,6 +242,11 @@ int rtc_check_code_object(const void *code, size_t len, std::string *why, uint32
         *why = "the code object declares RC_SUMS and defines no rc_user_dk_sums_pass kernel";
         return RC_EINVAL;
     }
+    if (fb_marker && (fb_size < 2 || fb_size > DK_MAX_FEEDBACK + 1)) {
+        *why = "the code object declares an RC_FEEDBACK outside 1 ... " + std::to_string(DK_MAX_FEEDBACK);
+        return RC_EINVAL;
+    }
+    if (feedback) *feedback = (uint32_t)(fb_size - 1);
     if (history) *history = (uint32_t)(hist_size - 1);
     if (cross) *cross = chan;
     if (sums) *sums = (uint32_t)(sums_size - 1);
@@ -249,15 +260,17 @@ struct UserModule {
     uint32_t history = 0;
     bool cross = false;
     uint32_t sums = 0;
+    uint32_t feedback = 0;
 };
 
 int rtc_load(const void *code, size_t len, UserModule **out, std::string *why) {
     *out = nullptr;
     uint32_t history = 0;
     bool cross = false;
-    uint32_t sums = 0;
-    if (int rc = rtc_check_code_object(code, len, why, &history, &cross, &sums)) return rc;
+    uint32_t sums = 0, feedback = 0;
+    if (int rc = rtc_check_code_object(code, len, why, &history, &cross, &sums, &feedback)) return rc;
     UserModule *m = new UserModule;
+    m->feedback = feedback;
     m->history = history;
     m->cross = cross;
     m->sums = sums;
@@ -286,6 +299,7 @@ void rtc_unload(UserModule *m) {
 uint32_t rtc_history(const UserModule *m) { return m ? m->history : 0; }
 bool rtc_cross(const UserModule *m) { return m && m->cross; }
 uint32_t rtc_sums(const UserModule *m) { return m ? m->sums : 0; }
+uint32_t rtc_feedback(const UserModule *m) { return m ? m->feedback : 0; }
 
 hipError_t rtc_launch(const UserModule *m, UserDkArgs a, uint64_t rows, hipStream_t s) {
     const uint64_t per_launch = 32768;  // grid.y limit, as launch_dev_kernel
@@ -308,6 +322,28 @@ hipError_t rtc_launch_sums(const UserModule *m, UserDkArgs a, uint64_t rows, hip
         void *args[] = {&a};
         const hipError_t e = hipModuleLaunchKernel(m->fn_sums, 1, gy, 1, 256, 1, 1, 0, s, args, nullptr);
         if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t rtc_launch_feedback(const UserModule *m, UserDkArgs a, uint32_t n_channels, bool per_hop, hipStream_t s,
+                               uint32_t *launches) {
+    *launches = 0;
+    if (!m->feedback) return hipErrorInvalidDeviceFunction;
+    const uint32_t hops = (uint32_t)a.hop_count;  // (a chunk holds at most 32768 hops)
+    const uint32_t per_launch = 32768;            // grid.y limit, as rtc_launch
+    const uint32_t gx = per_hop ? (a.n + 255) / 256 : 1;
+    for (uint32_t h0 = 0; h0 < hops; h0 += per_hop ? 1 : hops) {
+        a.fb_hop_first = h0;
+        a.fb_hop_count = per_hop ? 1 : hops;
+        for (uint32_t c0 = 0; c0 < n_channels; c0 += per_launch) {
+            a.row_first = c0;
+            const unsigned gy = n_channels - c0 < per_launch ? n_channels - c0 : per_launch;
+            void *args[] = {&a};
+            const hipError_t e = hipModuleLaunchKernel(m->fn, gx, gy, 1, 256, 1, 1, 0, s, args, nullptr);
+            if (e != hipSuccess) return e;
+            ++*launches;
+        }
     }
     return hipSuccess;
 }

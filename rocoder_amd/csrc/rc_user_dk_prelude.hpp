@@ -34,6 +34,18 @@
 // Inf propagate as that arithmetic gives. The order depends on N alone, so the bits of a sum do not depend on the launch,
 // chunk, range, stream batch or shard that computed it. The wrapper records S in the code object as the size of the
 // symbol rc_user_dk_sums (S + 1 bytes, present only when S > 0), and adds the kernel rc_user_dk_sums_pass.
+//
+// A source that says `#define RC_FEEDBACK F` (1 ... RC_DK_MAX_FEEDBACK; absent or 0: none) may read its own earlier
+// outputs: X.out(d) is the spectrum rc_apply returned for hop h.hop - d of the same channel, an rc_spectrum whose []
+// takes any index modulo N; h.feedback is F. The engine keeps F + 1 rows of N bins per channel, addressed by hop mod
+// (F + 1), and runs the hops of a channel in order (rc_engine_load_device_kernel states the order rule). X.out(d) reads
+// (0, 0) where d == 0, where d > F, where h.hop - d < 0, where hop h.hop - d lies before the first hop this kernel ran
+// since it was loaded or since its channel restarted at hop 0, where the source did not declare RC_FEEDBACK (the call
+// still compiles), for a single frame (rc_engine_resynth), inside rc_sum_term, and for X.channel(c).out(d) and
+// X.past(p).out(d) with c another channel or p > 0: out() belongs to X itself. An out spectrum is bins only: its
+// past(), channel() and out() read (0, 0) and its sum() reads 0, whatever their argument. X.out(d) composes with
+// RC_HISTORY, RC_CROSS_CHANNEL and RC_SUMS on X. The wrapper records F in the code object as the size of the symbol
+// rc_user_dk_feedback (F + 1 bytes, present only when F > 0).
 R"rc_prelude(
 typedef __hip_internal::uint32_t uint32_t;
 typedef __hip_internal::int32_t int32_t;
@@ -71,7 +83,8 @@ struct rc_spectrum {
     // the spectrum d hops earlier in the same channel; past(0) is this one
     __device__ rc_spectrum past(uint32_t d) const {
         rc_spectrum s = *this;
-        if (d > past_) {
+        if (d) s.fb_n_ = 0;
+        if (d > past_ || out_) {
             s.zero_ = true;
             s.past_ = 0;
         } else {
@@ -84,7 +97,9 @@ struct rc_spectrum {
     // the same hop of channel c of the job; channel(h.channel) is this one
     __device__ rc_spectrum channel(uint32_t c) const {
         rc_spectrum s = *this;
+        if (out_) s.zero_ = true;
         if (c == ch_) return s;
+        s.fb_n_ = 0;
         if (c - ch_lo_ >= ch_n_) {
             s.zero_ = true;
         } else {
@@ -97,6 +112,22 @@ struct rc_spectrum {
     // sum i of this hop (RC_SUMS, rc_sum_term): 0.f where i >= RC_SUMS, without the declaration, and where this
     // spectrum reads (0, 0)
     __device__ float sum(uint32_t i) const { return (zero_ || i >= n_sums_) ? 0.f : sums_[i]; }
+    // what rc_apply returned for the hop d before this one in the same channel (RC_FEEDBACK): (0, 0) where d == 0 or
+    // d > RC_FEEDBACK, before hop 0 and before the kernel's first hop, without the declaration, and for any spectrum
+    // but rc_apply's own X
+    __device__ rc_spectrum out(uint32_t d) const {
+        rc_spectrum s = *this;
+        s.out_ = true;
+        s.past_ = 0;
+        s.ch_lo_ = ch_;
+        s.ch_n_ = 1;
+        s.sums_ = nullptr;
+        s.n_sums_ = 0;
+        s.fb_n_ = 0;
+        if (zero_ || out_ || d == 0 || d > fb_n_ || d > fb_hop_) s.zero_ = true;
+        else s.p_ = fb_ + ((fb_hop_ - d) % (uint64_t)(fb_n_ + 1u)) * n;
+        return s;
+    }
     uint32_t past_;  // rows in front of p_ that past() may reach
     bool zero_;      // a hop outside the declared history or before the stream, a channel outside the block: (0, 0)
     uint32_t ch_;            // the channel p_ belongs to
@@ -104,6 +135,13 @@ struct rc_spectrum {
     uint32_t ch_rows_;       // rows from one channel of the block to the next
     const float *sums_;      // the n_sums_ sums of the row p_ (rows of sums lie as the rows of spectra do)
     uint32_t n_sums_;        // the declared RC_SUMS; 0 without it and inside rc_sum_term
+    // The channel's ring of earlier outputs, [fb_n_ + 1][n], row = hop mod (fb_n_ + 1). A plain pointer on purpose, never
+    // __restrict__, __ldg or an invariant load: a wave-uniform index such as X.out(1)[0] could otherwise become a scalar
+    // load, and a scalar load does not see the vector stores the previous hop of the same launch made to the ring.
+    const float2 *fb_;
+    uint64_t fb_hop_;        // the hop X stands for
+    uint32_t fb_n_;          // hops out() may reach back: RC_FEEDBACK for rc_apply's X in a job, else 0
+    bool out_;               // an out spectrum: bins only
 };
 
 // What the hop is: window length, channel, hop index k (the k of rc_phase_key), the launch's time and the params.
@@ -116,6 +154,7 @@ struct rc_hop {
     uint32_t n_params;
     uint32_t history;  // the declared RC_HISTORY
     uint32_t channels;  // rc_config::channels under RC_CROSS_CHANNEL, else 0
+    uint32_t feedback;  // the declared RC_FEEDBACK
     const float *params_;
     __device__ float param(uint32_t i) const { return i < n_params ? params_[i] : 0.f; }
 };
@@ -149,5 +188,20 @@ struct rc_dk_args_sums : rc_dk_args_channels {
     const float *sums;
     uint32_t n_sums;  // RC_SUMS
     uint32_t pad3_;
+};
+
+#define RC_DK_MAX_FEEDBACK 4
+
+// the argument block of a kernel that declares RC_FEEDBACK, whatever else it declares. `state` is the ring of every
+// channel of the job, [rc_config::channels][feedback + 1][n]: the output of hop k of channel c lies in row
+// c * (feedback + 1) + k mod (feedback + 1). A launch runs hops hop_first + fb_hop_first ... of fb_hop_count hops of
+// each of its channels, one after the other; row_first is then the first channel of the launch, counted from ch_first.
+// A single frame (rc_engine_resynth) has no ring: state is null and feedback 0. Host mirror: rc::UserDkArgs.
+struct rc_dk_args_feedback : rc_dk_args_sums {
+    float2 *state;
+    uint32_t feedback;      // RC_FEEDBACK, or 0 for a single frame
+    uint32_t fb_hop_first;  // counted from hop_first
+    uint32_t fb_hop_count;
+    uint32_t pad4_;
 };
 )rc_prelude"

@@ -5,6 +5,11 @@
 // Under RC_SUMS a second kernel, rc_user_dk_sums_pass, runs in front of it: one workgroup per row of the input block
 // (halo rows and analysed-only channels included) adds up the row's rc_sum_term values in a fixed order and stores the
 // S floats that X.sum(i) reads.
+// Under RC_FEEDBACK rc_user_dk is another kernel text: grid (x, channels); it walks a sub-range of the chunk's hops of its
+// channel in order, with a barrier between two hops, and writes every Y[j] to the output block and to the channel's ring
+// row, which X.out(d) of the later hops reads. The host launches it per hop with x = ceil(n / 256) (stream order is the
+// dependency) or once per chunk with x = 1 (one workgroup per channel; the barrier is the dependency). Nothing waits
+// between workgroups.
 R"rc_wrapper(
 #line 1 "rc_user_dk_wrapper"
 #ifndef RC_HISTORY
@@ -22,6 +27,11 @@ static_assert((RC_CROSS_CHANNEL) == 0 || (RC_CROSS_CHANNEL) == 1, "RC_CROSS_CHAN
 #define RC_SUMS 0
 #endif
 static_assert((RC_SUMS) >= 0 && (RC_SUMS) <= RC_DK_MAX_SUMS, "RC_SUMS must be 0 ... RC_DK_MAX_SUMS (4) whole-hop sums");
+#ifndef RC_FEEDBACK
+#define RC_FEEDBACK 0
+#endif
+static_assert((RC_FEEDBACK) >= 0 && (RC_FEEDBACK) <= RC_DK_MAX_FEEDBACK,
+              "RC_FEEDBACK must be 0 ... RC_DK_MAX_FEEDBACK (4) earlier outputs");
 #if (RC_CROSS_CHANNEL)
 // the declaration, for the loader: the presence of this symbol
 extern "C" __device__ __attribute__((used)) char rc_user_dk_channels[1] = {};
@@ -29,6 +39,12 @@ extern "C" __device__ __attribute__((used)) char rc_user_dk_channels[1] = {};
 #if (RC_SUMS) > 0
 // the declared number of sums, for the loader: a symbol of RC_SUMS + 1 bytes, present only with sums
 extern "C" __device__ __attribute__((used)) char rc_user_dk_sums[(RC_SUMS) + 1] = {};
+#endif
+#if (RC_FEEDBACK) > 0
+// the declared feedback depth, for the loader: a symbol of RC_FEEDBACK + 1 bytes, present only with feedback
+extern "C" __device__ __attribute__((used)) char rc_user_dk_feedback[(RC_FEEDBACK) + 1] = {};
+typedef rc_dk_args_feedback rc_dk_args_t;
+#elif (RC_SUMS) > 0
 typedef rc_dk_args_sums rc_dk_args_t;
 #elif (RC_CROSS_CHANNEL)
 typedef rc_dk_args_channels rc_dk_args_t;
@@ -37,6 +53,76 @@ typedef rc_dk_args_history rc_dk_args_t;
 #else
 typedef rc_dk_args rc_dk_args_t;
 #endif
+#if (RC_FEEDBACK) > 0
+extern "C" __global__ __launch_bounds__(256) void rc_user_dk(const rc_dk_args_t a) {
+    const uint64_t ci = a.row_first + blockIdx.y;  // the channel, counted from ch_first
+    const uint32_t channel = a.ch_first + (uint32_t)ci;
+#if (RC_CROSS_CHANNEL)
+    const uint64_t ch = channel - a.in_ch_first;
+#else
+    const uint64_t ch = ci;
+#endif
+    // the channel's ring: plain pointers, no __restrict__ (rc_spectrum::fb_ says why)
+    float2 *ring = a.state ? a.state + (uint64_t)channel * (uint64_t)((RC_FEEDBACK) + 1) * a.n : nullptr;
+    rc_hop h;
+    h.n = a.n;
+    h.channel = channel;
+#if (RC_CROSS_CHANNEL)
+    h.channels = a.channels;
+#else
+    h.channels = 0;
+#endif
+    h.history = (RC_HISTORY);
+    h.feedback = (RC_FEEDBACK);
+    h.time_ms = a.time_ms;
+    h.n_params = a.n_params < RC_DK_MAX_PARAMS ? a.n_params : RC_DK_MAX_PARAMS;
+    h.params_ = a.params;
+    for (uint32_t i = 0; i < a.fb_hop_count; ++i) {
+        // hop k - 1's ring row is complete, and its reads of the row hop k overwrites are done, before hop k starts (with
+        // one hop per launch, the launches' order on the stream says the same)
+        if (i) __syncthreads();
+        const uint64_t hl = (uint64_t)a.fb_hop_first + i;
+        const uint64_t k = (uint64_t)a.hop_first + hl;
+        const uint64_t behind = a.halo + hl;
+        rc_spectrum X;
+        X.n = a.n;
+        X.mask_ = a.mask;
+        X.zero_ = false;
+        X.ch_ = channel;
+#if (RC_CROSS_CHANNEL)
+        X.ch_lo_ = a.in_ch_first;
+        X.ch_n_ = a.in_ch_count;
+        X.ch_rows_ = (uint32_t)a.in_rows;
+#else
+        X.ch_lo_ = channel;
+        X.ch_n_ = 1;
+        X.ch_rows_ = 0;
+#endif
+        X.p_ = a.in + (ch * a.in_rows + hl) * a.n;
+        X.past_ = (uint32_t)(behind < (uint64_t)(RC_HISTORY) ? behind : (uint64_t)(RC_HISTORY));
+        if (k < X.past_) X.past_ = (uint32_t)k;
+#if (RC_SUMS) > 0
+        X.sums_ = a.sums + (ch * a.in_rows + hl) * (uint64_t)(RC_SUMS);
+        X.n_sums_ = (RC_SUMS);
+#else
+        X.sums_ = nullptr;
+        X.n_sums_ = 0;
+#endif
+        X.fb_ = ring;
+        X.fb_hop_ = k;
+        X.fb_n_ = ring ? a.feedback : 0u;
+        X.out_ = false;
+        h.hop = k;
+        float2 *const y = a.out + (ci * a.hop_count + hl) * a.n;
+        float2 *const row = ring ? ring + (k % (uint64_t)((RC_FEEDBACK) + 1)) * a.n : nullptr;
+        for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < a.n; j += gridDim.x * 256u) {
+            const float2 v = rc_apply(X, j, h);
+            y[j] = v;
+            if (row) row[j] = v;
+        }
+    }
+}
+#else
 extern "C" __global__ __launch_bounds__(256) void rc_user_dk(const rc_dk_args_t a) {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
     if (j >= a.n) return;
@@ -81,6 +167,10 @@ extern "C" __global__ __launch_bounds__(256) void rc_user_dk(const rc_dk_args_t 
     X.sums_ = nullptr;
     X.n_sums_ = 0;
 #endif
+    X.fb_ = nullptr;
+    X.fb_hop_ = 0;
+    X.fb_n_ = 0;
+    X.out_ = false;
     rc_hop h;
     h.n = a.n;
     h.channel = channel;
@@ -91,11 +181,13 @@ extern "C" __global__ __launch_bounds__(256) void rc_user_dk(const rc_dk_args_t 
 #endif
     h.hop = (uint64_t)k;
     h.history = (RC_HISTORY);
+    h.feedback = 0;
     h.time_ms = a.time_ms;
     h.n_params = a.n_params < RC_DK_MAX_PARAMS ? a.n_params : RC_DK_MAX_PARAMS;
     h.params_ = a.params;
     a.out[base + j] = rc_apply(X, j, h);
 }
+#endif
 #if (RC_SUMS) > 0
 // The sums of every row of the input block: grid (1, rows), row r = a.row_first + blockIdx.y of
 // [in_ch_count][halo + hop_count]. Lane t adds the terms of bins t, t + 256, ... in double, ascending; the 256 partials
@@ -118,6 +210,10 @@ extern "C" __global__ __launch_bounds__(256) void rc_user_dk_sums_pass(const rc_
     X.ch_rows_ = 0;
     X.sums_ = nullptr;
     X.n_sums_ = 0;
+    X.fb_ = nullptr;
+    X.fb_hop_ = 0;
+    X.fb_n_ = 0;
+    X.out_ = false;
     rc_hop h;
     h.n = a.n;
     h.channel = channel;
@@ -128,6 +224,7 @@ extern "C" __global__ __launch_bounds__(256) void rc_user_dk_sums_pass(const rc_
 #endif
     h.hop = (uint64_t)(a.hop_first - (int64_t)a.halo + (int64_t)hl);
     h.history = (RC_HISTORY);
+    h.feedback = (RC_FEEDBACK);
     h.time_ms = a.time_ms;
     h.n_params = a.n_params < RC_DK_MAX_PARAMS ? a.n_params : RC_DK_MAX_PARAMS;
     h.params_ = a.params;

@@ -134,6 +134,16 @@ def device_kernel_sums(code: bytes) -> int:
     return 0
 
 
+def device_kernel_feedback(code: bytes) -> int:
+    """The feedback depth a code object from compile_device_kernel declares (`#define RC_FEEDBACK F` in its source:
+    rc_apply reads X.out(1..F), what it returned for the F hops before), 0 for a source without it. Pure Python: F is the
+    size of the ELF symbol rc_user_dk_feedback less one, and a code object without that symbol has none."""
+    for name, size in _code_object_symbols(code):
+        if name == b"rc_user_dk_feedback":
+            return max(0, size - 1)
+    return 0
+
+
 def device_kernel_history(code: bytes) -> int:
     """The history depth a code object from compile_device_kernel declares (`#define RC_HISTORY D` in its source: the
     earlier hops X.past(1..D) that rc_apply reads), 0 for a source without one. Pure Python: the depth is the size of
