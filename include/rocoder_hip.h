@@ -787,6 +787,9 @@ int rc_multi_set_device_kernel_params(rc_multi *m, const float *params, uint32_t
  * wave instruction takes on one SIMD in *ns_per_inst. Not on the reference's path. */
 int rc_calib_valu(int device, void *hip_stream, uint32_t launches, float *ms_per_launch, float *ns_per_inst);
 
+/* ---- time maps: rc_engine_set_time_map, rc_time_map_output_len, rc_time_map_curve ------------ */
+#include "rocoder_hip_timemap.h"
+
 #ifdef __cplusplus
 }
 #endif

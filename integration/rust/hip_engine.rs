@@ -164,6 +164,17 @@ extern "C" {
     pub fn rc_multi_set_device_kernel_params(m: *mut RcMulti, params: *const f32, n_params: u32) -> c_int;
 }
 
+// `include/rocoder_hip_timemap.h` (included by rocoder_hip.h): time maps. Hop k reads its window at hop_pos[k] - a hold,
+// a reversed passage, a scrub, a varying factor; engine state like the fade, null or n_hops == 0 clears it. It applies to
+// the whole-job entries; _device_range and the streaming seam refuse while one is set. The two helpers touch no device.
+#[link(name = "rocoder_hip")]
+extern "C" {
+    pub fn rc_engine_set_time_map(e: *mut RcEngine, hop_pos: *const i64, n_hops: usize) -> c_int;
+    pub fn rc_time_map_output_len(cfg: *const RcConfig, n_hops: usize) -> usize;
+    pub fn rc_time_map_curve(cfg: *const RcConfig, in_len: usize, at: *const f64, factor: *const f64, n_points: usize,
+                             hop_pos: *mut i64, cap: usize, n_hops: *mut usize) -> c_int;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // safe-ish helpers shared by stretcher_hip.rs
 

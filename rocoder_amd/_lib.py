@@ -165,6 +165,14 @@ SYMBOLS = {
     "rc_multi_set_device_kernel_params": (C.c_int, [_eng, _fp, C.c_uint32]),
 }
 
+# ... and every symbol include/rocoder_hip_timemap.h declares (rocoder_hip.h includes it)
+TIME_MAP_SYMBOLS = {
+    "rc_engine_set_time_map": (C.c_int, [_eng, C.POINTER(C.c_int64), _sz]),
+    "rc_time_map_output_len": (_sz, [C.POINTER(rc_config), _sz]),
+    "rc_time_map_curve": (C.c_int, [C.POINTER(rc_config), _sz, C.POINTER(C.c_double), C.POINTER(C.c_double), _sz,
+                                    C.POINTER(C.c_int64), _sz, C.POINTER(_sz)]),
+}
+
 _lib = None
 
 
@@ -188,7 +196,7 @@ def _load(path: str) -> C.CDLL:
     except ImportError:
         pass
     L = C.CDLL(path)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(TIME_MAP_SYMBOLS.items()):
         fn = getattr(L, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

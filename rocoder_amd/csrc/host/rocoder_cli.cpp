@@ -13,7 +13,9 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <cctype>
 #include <chrono>
 #include <cmath>
@@ -200,6 +202,10 @@ struct FramesApi {
     // (--limit only: may be missing, both or neither)
     decltype(&rc_engine_set_output_limiter) set_limiter = nullptr;
     decltype(&rc_engine_last_limiter_stats) limiter_stats = nullptr;
+    // (--factor-curve / --time-map only: may be missing, all or none)
+    decltype(&rc_engine_set_time_map) set_time_map = nullptr;
+    decltype(&rc_time_map_output_len) time_map_output_len = nullptr;
+    decltype(&rc_time_map_curve) time_map_curve = nullptr;
     decltype(&rc_host_alloc) alloc = nullptr;
     decltype(&rc_host_free) free = nullptr;
 };
@@ -223,6 +229,9 @@ static const FramesApi &frames_api() {
         a.resample_table = (decltype(a.resample_table))dlsym(RTLD_DEFAULT, "rc_resample_table");
         a.set_limiter = (decltype(a.set_limiter))dlsym(RTLD_DEFAULT, "rc_engine_set_output_limiter");
         a.limiter_stats = (decltype(a.limiter_stats))dlsym(RTLD_DEFAULT, "rc_engine_last_limiter_stats");
+        a.set_time_map = (decltype(a.set_time_map))dlsym(RTLD_DEFAULT, "rc_engine_set_time_map");
+        a.time_map_output_len = (decltype(a.time_map_output_len))dlsym(RTLD_DEFAULT, "rc_time_map_output_len");
+        a.time_map_curve = (decltype(a.time_map_curve))dlsym(RTLD_DEFAULT, "rc_time_map_curve");
         a.alloc = (decltype(a.alloc))dlsym(RTLD_DEFAULT, "rc_host_alloc");
         a.free = (decltype(a.free))dlsym(RTLD_DEFAULT, "rc_host_free");
         if (!a.stretch || !a.alloc || !a.free) throw std::runtime_error("--frames-on-gpu: the engine library has no rc_engine_stretch_frames");
@@ -1138,6 +1147,11 @@ struct Opt {  // src/main.rs:27-122
     std::optional<std::vector<uint32_t>> channel_map;
     // recorder::auto_split_mono (src/recorder.rs:118-144, in front of the autocrop, :64-70): measured on the GPU (--frames-on-gpu)
     bool split_mono = false;
+    // not in the reference: per-hop input positions (--frames-on-gpu; rc_engine_set_time_map). --factor-curve "t:f,t:f,...": the
+    // factor is f at input time t (the duration grammar, behind -s / --autocrop), linear in between; --time-map: a file of
+    // positions in input frames, one per line
+    std::optional<std::string> factor_curve, time_map_file;
+    bool factor_given = false;
     std::optional<float> normalize;  // not in the reference: the output's peak is brought to this level on the GPU (--frames-on-gpu)
     // not in the reference (-p moves octaves, and decimates with no filter): pitch by any ratio and another output rate, by
     // band-limited resampling of the result on the GPU (--frames-on-gpu; rc_engine_set_output_resample)
@@ -1212,6 +1226,14 @@ void usage() {
             "        --pitch-cents <c>              The same with the ratio 2^(c / 1200): 100 is a semitone up\n"
             "        --output-rate <Hz>             With --frames-on-gpu: write the output at this sample rate (resampled on the\n"
             "                                       GPU in the same pass as --pitch-ratio); the pitch and the duration stay\n"
+            "        --factor-curve <t:f,t:f,...>   With --frames-on-gpu: a stretch factor that varies along the input: f at input time t\n"
+            "                                       (a duration, behind -s / --autocrop), linear in between, constant outside the\n"
+            "                                       points; takes the place of -f (an explicit -f is refused). Under either map\n"
+            "                                       flag --fade-output fades out into the map's last frame, and --pitch-ratio /\n"
+            "                                       --pitch-cents are refused (they work through -f, which a map ignores)\n"
+            "        --time-map <file>              With --frames-on-gpu: hop k reads the input at the k-th position of the file: one\n"
+            "                                       integer (input frames) per line, # comments; positions may repeat (a hold),\n"
+            "                                       decrease (reverse), be negative or lie past the end (silence)\n"
             "        --limit <ceiling | dB>         With --frames-on-gpu: a look-ahead peak limiter on the GPU behind --fade-output and in\n"
             "                                       front of --normalize, --dither and the quantiser: no sample leaves above the\n"
             "                                       ceiling (1 = full scale, or -0.3dB), frames away from an over keep their bits;\n"
@@ -1335,7 +1357,11 @@ int run(int argc, char **argv) {
         }
         else if (a == "-w" || a == "--window") o.window_len = (size_t)strtoull(need(i).c_str(), nullptr, 10);
         else if (a == "-b" || a == "--buffer") o.buffer_ms = dur(need(i));
-        else if (a == "-f" || a == "--factor") o.factor = strtof(need(i).c_str(), nullptr);
+        else if (a == "-f" || a == "--factor") {
+            o.factor = strtof(need(i).c_str(), nullptr);
+            o.factor_given = true;
+        } else if (a == "--factor-curve") o.factor_curve = need(i);
+        else if (a == "--time-map") o.time_map_file = need(i);
         else if (a == "-p" || a == "--pitch_multiple" || a == "--pitch-multiple") o.pitch_multiple = atoi(need(i).c_str());
         else if (a == "-a" || a == "--amplitude") o.amplitude = strtof(need(i).c_str(), nullptr);
         else if (a == "-i" || a == "--input") o.input = need(i);
@@ -1517,6 +1543,13 @@ int run(int argc, char **argv) {
     if (o.channel_map && !o.frames_on_gpu) throw std::runtime_error("--channel-map needs --frames-on-gpu");
     // (the channels are measured by the engine on the raw frame block, and the copy is the engine's channel map)
     if (o.split_mono && !o.frames_on_gpu) throw std::runtime_error("--split-mono needs --frames-on-gpu");
+    // (the map is state of the engine's whole-job calls: the streaming seam the host path runs on refuses one)
+    if ((o.factor_curve || o.time_map_file) && !o.frames_on_gpu) throw std::runtime_error("--factor-curve / --time-map needs --frames-on-gpu");
+    if (o.factor_curve && o.time_map_file) throw std::runtime_error("--factor-curve cannot be combined with --time-map: one map");
+    if (o.factor_curve && o.factor_given) throw std::runtime_error("--factor-curve takes the place of -f: give one of them");
+    // (--pitch-ratio keeps the duration by stretching at factor * ratio: a map ignores the factor, so the two cannot compose)
+    if ((o.factor_curve || o.time_map_file) && o.pitch_ratio)
+        throw std::runtime_error("--pitch-ratio / --pitch-cents cannot be combined with --factor-curve / --time-map: a map sets the speed, not -f");
     if (o.dither_seed && !o.dither_given) throw std::runtime_error("--dither-seed needs --dither");
     // dither belongs in front of a quantiser of 8, 16 or 24 bits: f32 has none, and a step of i32 lies below an f32's precision
     auto check_dither_format = [&](uint32_t fmt) {
@@ -1707,6 +1740,66 @@ int run(int argc, char **argv) {
             lap("autocrop");
         }
         size_t cap = rc_offline_output_len(&cfg, raw_count);
+        if (o.factor_curve || o.time_map_file) {
+            const FramesApi &api = frames_api();
+            if (!api.set_time_map || !api.time_map_output_len || !api.time_map_curve)
+                throw std::runtime_error("--factor-curve / --time-map: the engine library has no rc_engine_set_time_map");
+            std::vector<int64_t> pos;
+            if (o.factor_curve) {  // "t:f,t:f,...": t in the duration grammar -> input frames, as duration_to_sample's product in doubles
+                std::vector<double> at, fac;
+                size_t b = 0;
+                for (;;) {
+                    const size_t c = o.factor_curve->find(',', b);
+                    const std::string pt = o.factor_curve->substr(b, c == std::string::npos ? c : c - b);
+                    const size_t colon = pt.rfind(':');
+                    uint64_t ms = 0;
+                    char *end = nullptr;
+                    const double f = colon == std::string::npos ? 0.0 : strtod(pt.c_str() + colon + 1, &end);
+                    if (colon == std::string::npos || colon == 0 || !end || *end || end == pt.c_str() + colon + 1 ||
+                        !parse_duration_ms(pt.substr(0, colon), &ms))
+                        throw std::runtime_error("--factor-curve takes points t:f,t:f,... (t a duration, f a factor), not " + pt);
+                    at.push_back((double)ms / 1000.0 * (double)spec.sample_rate);
+                    fac.push_back(f);
+                    if (c == std::string::npos) break;
+                    b = c + 1;
+                }
+                size_t K = 0;
+                int rc = api.time_map_curve(&cfg, raw_count, at.data(), fac.data(), at.size(), nullptr, 0, &K);
+                if (rc == RC_ECAPACITY) {
+                    pos.resize(K);
+                    rc = api.time_map_curve(&cfg, raw_count, at.data(), fac.data(), at.size(), pos.data(), K, &K);
+                }
+                if (rc != RC_OK)
+                    throw std::runtime_error("--factor-curve: times ascending and at least 0, factors in [2^-10, 2^20], at most 2^28 hops");
+            } else {
+                FILE *mf = fopen(o.time_map_file->c_str(), "r");
+                if (!mf) throw std::runtime_error("cannot open " + *o.time_map_file);
+                char line[256];
+                size_t line_no = 0;
+                while (fgets(line, sizeof line, mf)) {
+                    ++line_no;
+                    if (char *hash = strchr(line, '#')) *hash = 0;
+                    char *q = line, *end = nullptr;
+                    while (*q == ' ' || *q == '\t' || *q == '\r' || *q == '\n') ++q;
+                    if (!*q) continue;
+                    errno = 0;
+                    const long long v = strtoll(q, &end, 10);
+                    while (*end == ' ' || *end == '\t' || *end == '\r' || *end == '\n') ++end;
+                    if (end == q || *end || errno) {
+                        fclose(mf);
+                        throw std::runtime_error(*o.time_map_file + ":" + std::to_string(line_no) + ": not an integer position");
+                    }
+                    pos.push_back((int64_t)v);
+                }
+                fclose(mf);
+                if (pos.empty()) throw std::runtime_error(*o.time_map_file + " holds no position");
+            }
+            if (api.set_time_map(eng.h, pos.data(), pos.size()) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+            cap = api.time_map_output_len(&cfg, pos.size());
+            fprintf(stderr, "time map: %zu hops, %zu frames out, input positions [%lld, %lld]\n", pos.size(), cap,
+                    (long long)*std::min_element(pos.begin(), pos.end()), (long long)*std::max_element(pos.begin(), pos.end()));
+            lap("time map");
+        }
         const uint32_t out_sb = pcm_sample_bytes(out_fmt);
         AudioSpec out_spec = spec;  // the output file's: --output-rate
         if (o.pitch_ratio || o.output_rate) {
@@ -1733,6 +1826,8 @@ int run(int argc, char **argv) {
             const size_t fade = (size_t)((float)((double)o.fade_ms / 1000.0) * (float)out_spec.sample_rate);
             size_t expected = (size_t)((float)raw_count * o.factor);
             if (out_spec.sample_rate != spec.sample_rate) expected = (size_t)((double)expected * (double)out_spec.sample_rate / (double)spec.sample_rate);
+            // under a time map the job ends where the map ends, whatever -f says: the fade-out runs into the output's last frame
+            if (o.factor_curve || o.time_map_file) expected = cap;
             const bool in_fits = fade <= cap, out_fits = expected <= cap && expected >= fade;
             if (!in_fits) fprintf(stderr, "Fade in parameters out of bounds, ignoring.\n");
             if (!out_fits) fprintf(stderr, "Fade out parameters out of bounds, ignoring.\n");

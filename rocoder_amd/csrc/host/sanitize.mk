@@ -7,7 +7,7 @@
 ROOT := ../../..
 CXX  ?= g++
 COMMON := -g -O1 -std=c++17 -Wall -fno-omit-frame-pointer rocoder_cli.cpp -ldl -lpthread
-all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../bin/engine_tsan ../../bin/engine_dk_asan ../../bin/engine_xch_asan ../../bin/engine_frames_asan ../../bin/engine_frames_pcm_asan ../../bin/engine_frames_norm_asan ../../bin/engine_frames_fade_asan ../../bin/engine_frames_power_asan ../../bin/engine_frames_map_asan ../../bin/engine_frames_dither_asan ../../bin/engine_frames_resample_asan ../../bin/engine_frames_limit_asan ../../bin/engine_frames_loud_asan ../../bin/engine_dk_sums_asan ../../bin/engine_dk_fb_asan
+all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../bin/engine_tsan ../../bin/engine_dk_asan ../../bin/engine_xch_asan ../../bin/engine_frames_asan ../../bin/engine_frames_pcm_asan ../../bin/engine_frames_norm_asan ../../bin/engine_frames_fade_asan ../../bin/engine_frames_power_asan ../../bin/engine_frames_map_asan ../../bin/engine_frames_dither_asan ../../bin/engine_frames_resample_asan ../../bin/engine_frames_limit_asan ../../bin/engine_frames_loud_asan ../../bin/engine_dk_sums_asan ../../bin/engine_dk_fb_asan ../../bin/engine_timemap_asan ../../bin/engine_timemap_tsan
 ../../bin/rocoder_asan: rocoder_cli.cpp $(ROOT)/include/rocoder_hip.h ../../librocoder_hip.so
 	mkdir -p ../../bin
 	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(COMMON) -o $@ -L../.. -lrocoder_hip \
@@ -25,10 +25,11 @@ ENGINE_FLAGS := -g -O1 -std=c++17 -Wall -Wno-unused-function -fno-omit-frame-poi
     -I/opt/rocm/include -x c++
 ASAN := -fsanitize=address,undefined -fno-sanitize-recover=undefined
 TSAN := -fsanitize=thread
-ENGINE_HDR := ../rc_kernels.h ../rc_long.h ../rc_frames.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h
+ENGINE_HDR := ../rc_kernels.h ../rc_long.h ../rc_frames.h ../rc_timemap.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h $(ROOT)/include/rocoder_hip_timemap.h
 # the engine and the stubs: compiled once per sanitizer, linked into every driver's program
 ENGINE_PARTS := rc_engine rc_rtc hip_stub hip_stub_long hip_stub_frames hip_stub_frames_pcm hip_stub_frames_norm \
-    hip_stub_frames_fade hip_stub_frames_power hip_stub_frames_map hip_stub_frames_dither hip_stub_frames_resample hip_stub_frames_limit hip_stub_frames_loud hip_stub_rtc
+    hip_stub_frames_fade hip_stub_frames_power hip_stub_frames_map hip_stub_frames_dither hip_stub_frames_resample hip_stub_frames_limit hip_stub_frames_loud hip_stub_rtc \
+    hip_stub_timemap rc_timemap_curve
 ENGINE_ASAN_OBJ := $(ENGINE_PARTS:%=../../bin/%.asan.o)
 ENGINE_TSAN_OBJ := $(ENGINE_PARTS:%=../../bin/%.tsan.o)
 vpath %.cpp .. $(ROOT)/tests/c
@@ -79,6 +80,27 @@ ENGINE_FB_ASAN_OBJ := $(filter-out ../../bin/hip_stub_rtc.asan.o,$(ENGINE_ASAN_O
 ../../bin/hip_stub_rtc_fb.asan.o: $(ROOT)/tests/c/hip_stub_rtc_fb.h
 ../../bin/engine_dk_fb_asan: $(ROOT)/tests/c/engine_host_driver_dk_fb.cpp $(ENGINE_FB_ASAN_OBJ) $(ENGINE_HDR) $(ROOT)/tests/c/hip_stub_rtc_fb.h
 	$(CXX) $(ASAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_FB_ASAN_OBJ) -o $@ -lpthread -ldl
+#   timemap      rc_engine_set_time_map on the whole-job entries (hip_stub_timemap.cpp's gather launcher really gathers on the
+#                CPU and logs its launches), over an engine built with -DRC_TEST_HOOKS=1 for rc_test_time_map_chunk_windows
+#                (rc_timemap_curve.cpp, a bit-exact host definition, is built without contraction here too)
+../../bin/rc_timemap_curve.%.o: ENGINE_FLAGS += -ffp-contract=off
+../../bin/rc_engine.hooks.asan.o: ../rc_engine.cpp $(ENGINE_HDR)
+	mkdir -p ../../bin
+	$(CXX) $(ASAN) $(ENGINE_FLAGS) -DRC_TEST_HOOKS=1 -c $< -o $@
+../../bin/rc_engine.hooks.tsan.o: ../rc_engine.cpp $(ENGINE_HDR)
+	mkdir -p ../../bin
+	$(CXX) $(TSAN) $(ENGINE_FLAGS) -DRC_TEST_HOOKS=1 -c $< -o $@
+#                This program alone is linked with --wrap for rc::launch_hop, rc::launch_prep and hipMemcpyAsync: the engine's
+#                calls of them pass through hip_stub_timemap_hops.cpp, which logs what run_hops hands on and what the copy
+#                workers upload, and then reach hip_stub.cpp's own functions. hip_stub.cpp and the other drivers are untouched.
+ENGINE_TM_ASAN_OBJ := $(filter-out ../../bin/rc_engine.asan.o,$(ENGINE_ASAN_OBJ)) ../../bin/rc_engine.hooks.asan.o ../../bin/hip_stub_timemap_hops.asan.o
+ENGINE_TM_TSAN_OBJ := $(filter-out ../../bin/rc_engine.tsan.o,$(ENGINE_TSAN_OBJ)) ../../bin/rc_engine.hooks.tsan.o ../../bin/hip_stub_timemap_hops.tsan.o
+TM_WRAP := -Wl,--wrap=_ZN2rc10launch_hopEiNS_7HopModeERKNS_9HopParamsEP12ihipStream_t \
+    -Wl,--wrap=_ZN2rc11launch_prepERKNS_10PrepParamsEP12ihipStream_t -Wl,--wrap=hipMemcpyAsync
+../../bin/engine_timemap_asan: $(ROOT)/tests/c/engine_host_driver_timemap.cpp $(ENGINE_TM_ASAN_OBJ) $(ENGINE_HDR)
+	$(CXX) $(ASAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_TM_ASAN_OBJ) $(TM_WRAP) -o $@ -lpthread -ldl
+../../bin/engine_timemap_tsan: $(ROOT)/tests/c/engine_host_driver_timemap.cpp $(ENGINE_TM_TSAN_OBJ) $(ENGINE_HDR)
+	$(CXX) $(TSAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_TM_TSAN_OBJ) $(TM_WRAP) -o $@ -lpthread -ldl
 ../../bin/engine_%_asan: $(ROOT)/tests/c/engine_host_driver_%.cpp $(ENGINE_ASAN_OBJ) $(ENGINE_HDR)
 	$(CXX) $(ASAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_ASAN_OBJ) -o $@ -lpthread -ldl
 ../../bin/engine_%_tsan: $(ROOT)/tests/c/engine_host_driver_%.cpp $(ENGINE_TSAN_OBJ) $(ENGINE_HDR)

@@ -232,6 +232,40 @@ def offline_output_len(in_len: int, **kw) -> int:
     return int(_lib.lib().rc_offline_output_len(C.byref(cfg), in_len))
 
 
+def time_map_output_len(n_hops: int, **kw) -> int:
+    """The output frames of a time map of `n_hops` hops under the configuration `kw` (rc_time_map_output_len): n_hops /
+    hops_per_window * window_out_len, 0 where n_hops is no multiple of hops_per_window. Pure host code."""
+    if not 0 <= int(n_hops) < 2 ** 64:
+        raise ValueError("n_hops is an unsigned integer")
+    cfg, _keep = make_config(**kw)
+    return int(_lib.lib().rc_time_map_output_len(C.byref(cfg), int(n_hops)))
+
+
+def time_map_curve(in_len: int, at, factors, **kw) -> np.ndarray:
+    """The time map (int64 [K], what `Engine.set_time_map` takes) of a stretch factor that varies along an input of
+    `in_len` samples (rc_time_map_curve; the definition is in include/rocoder_hip.h): the factor is `factors[i]` at input
+    sample `at[i]`, linear in between and constant outside the points; hop k + 1 lies N / (2 psf(f(q_k))) samples behind
+    hop k, in doubles, and the map ends with the window in which the input runs out. Pure host code. Points out of order,
+    a factor outside [2^-10, 2^20] or a curve of 2^28 hops or more raise (RC_EINVAL)."""
+    a = np.ascontiguousarray(at, np.float64).reshape(-1)
+    f = np.ascontiguousarray(factors, np.float64).reshape(-1)
+    if a.size != f.size or a.size == 0:
+        raise ValueError("at and factors hold the same number of points, at least one")
+    if not 0 <= int(in_len) < 2 ** 64:
+        raise ValueError("in_len is an unsigned integer")
+    cfg, _keep = make_config(**kw)
+    L = _lib.lib()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+    n = C.c_size_t(0)
+    rc = L.rc_time_map_curve(C.byref(cfg), int(in_len), a.ctypes.data_as(dp), f.ctypes.data_as(dp), a.size, None, 0, C.byref(n))
+    if rc != _lib.RC_ECAPACITY:
+        check(rc, L)
+    out = np.empty(n.value, np.int64)
+    check(L.rc_time_map_curve(C.byref(cfg), int(in_len), a.ctypes.data_as(dp), f.ctypes.data_as(dp), a.size, out.ctypes.data_as(ip),
+                              out.size, C.byref(n)), L)
+    return out
+
+
 def resample_len(n: int, num: int, den: int) -> int:
     """The frames a resample of `n` frames by the step num / den gives (rc_resample_len): the m with m * num / den < n."""
     if not (0 <= int(n) < 2 ** 64 and 0 <= int(num) < 2 ** 32 and 0 <= int(den) < 2 ** 32):
@@ -344,6 +378,7 @@ class Engine:
         self.window_len = int(self._cfg.window_len)
         self._resample = None  # set_output_resample: (num, den) while a step is set
         self._limiter = False  # set_output_limiter: a limiter is set
+        self._map_hops = None  # set_time_map: the hops of the map while one is set
 
     def close(self):
         for o in list((getattr(self, "_views", None) or {}).values()):
@@ -425,7 +460,30 @@ class Engine:
 
     # ---- offline
     def output_len(self, in_len: int) -> int:
+        """The frames of a whole job on `in_len` input frames; while a time map is set (set_time_map), the map's."""
+        if self._map_hops is not None:
+            return int(self._L.rc_time_map_output_len(C.byref(self._cfg), self._map_hops))
         return int(self._L.rc_offline_output_len(C.byref(self._cfg), in_len))
+
+    def set_time_map(self, hop_pos=None):
+        """Hop k of every whole job from now on reads its window at input sample `hop_pos[k]`, silence where that leaves
+        the input, instead of at k * sample_step_len (rc_engine_set_time_map; the definition is in
+        include/rocoder_hip.h): positions may repeat (a hold), decrease (reverse), be negative or lie past the end. The
+        number of hops is a multiple of `params.hops_per_window`, and the job has `output_len` = hops / hops_per_window *
+        window_out_len frames whatever its input length. It applies to `stretch_host`, `stretch_frames`,
+        `stretch_frames_loud` and `stretch_tensor` / `stretch_device_ptr`, under every output stage and kernel. While a
+        map is set `stretch_device_range_ptr` and the streaming calls raise (RC_EINVAL). None (or an empty list) clears
+        it. `time_map_curve` builds the map of a varying stretch factor. A bad length or a position beyond +-2^48 raises
+        (RC_EINVAL) and the previous map stays."""
+        if hop_pos is None or len(hop_pos) == 0:
+            self._check(self._L.rc_engine_set_time_map(self._h, None, 0))
+            self._map_hops = None
+            return
+        if any(not -2 ** 63 <= int(v) < 2 ** 63 for v in hop_pos):
+            raise ValueError("positions are signed 64-bit integers")
+        pos = np.ascontiguousarray(hop_pos, np.int64).reshape(-1)
+        self._check(self._L.rc_engine_set_time_map(self._h, pos.ctypes.data_as(C.POINTER(C.c_int64)), pos.size))
+        self._map_hops = int(pos.size)
 
     def _host_output_len(self, in_len: int) -> int:
         # what `stretch_host` and `stretch_frames` give: output_len, resampled where a step is set
@@ -1069,4 +1127,4 @@ def stretch(channels_in, window_len=16384, factor=1.0, amplitude=1.0, pitch_mult
 
 __all__ = ["AudioSpec", "AudioBus", "Engine", "ReFFT", "Stretcher", "StretcherProcessor", "stretch",
            "derive_params", "offline_output_len", "load_kernel_library", "RocoderError", "compile_device_kernel",
-           "DeviceKernelCompileError"]
+           "DeviceKernelCompileError", "time_map_output_len", "time_map_curve"]
