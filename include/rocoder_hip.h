@@ -790,6 +790,9 @@ int rc_calib_valu(int device, void *hip_stream, uint32_t launches, float *ms_per
 /* ---- time maps: rc_engine_set_time_map, rc_time_map_output_len, rc_time_map_curve ------------ */
 #include "rocoder_hip_timemap.h"
 
+/* ---- output warp: rc_engine_set_output_warp, rc_warp_table, rc_warp_curve ---------------------- */
+#include "rocoder_hip_warp.h"
+
 #ifdef __cplusplus
 }
 #endif

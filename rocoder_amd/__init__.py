@@ -5,6 +5,6 @@ from .stretcher import (AudioBus, AudioSpec, DeviceKernelCompileError, Engine, M
                         RocoderError, Stretcher, StretcherProcessor, autocrop_points, compile_device_kernel, derive_params,
                         device_kernel_cross_channel, device_kernel_feedback, device_kernel_history, device_kernel_sums,
                         load_kernel_library,
-                        offline_output_len, pinned_empty, split_mono_map, stretch, time_map_curve, time_map_output_len)
+                        offline_output_len, pinned_empty, split_mono_map, stretch, time_map_curve, time_map_output_len, warp_curve, warp_table)
 
 __version__ = "0.1.0"

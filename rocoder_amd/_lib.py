@@ -173,6 +173,14 @@ TIME_MAP_SYMBOLS = {
                                     C.POINTER(C.c_int64), _sz, C.POINTER(_sz)]),
 }
 
+# ... and every symbol include/rocoder_hip_warp.h declares (rocoder_hip.h includes it)
+WARP_SYMBOLS = {
+    "rc_engine_set_output_warp": (C.c_int, [_eng, C.POINTER(C.c_int64), _sz, _sz]),
+    "rc_warp_table": (C.c_int, [C.c_uint32, _fp, _sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rc_warp_curve": (C.c_int, [C.POINTER(rc_config), C.POINTER(C.c_int64), _sz, C.POINTER(C.c_double), C.POINTER(C.c_double), _sz, _sz,
+                                C.POINTER(C.c_int64), _sz, C.POINTER(_sz), C.POINTER(_sz)]),
+}
+
 _lib = None
 
 
@@ -196,7 +204,7 @@ def _load(path: str) -> C.CDLL:
     except ImportError:
         pass
     L = C.CDLL(path)
-    for name, (res, args) in list(SYMBOLS.items()) + list(TIME_MAP_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(TIME_MAP_SYMBOLS.items()) + list(WARP_SYMBOLS.items()):
         fn = getattr(L, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

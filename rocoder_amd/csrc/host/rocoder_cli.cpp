@@ -206,6 +206,9 @@ struct FramesApi {
     decltype(&rc_engine_set_time_map) set_time_map = nullptr;
     decltype(&rc_time_map_output_len) time_map_output_len = nullptr;
     decltype(&rc_time_map_curve) time_map_curve = nullptr;
+    // (--pitch-curve only: may be missing, both or neither)
+    decltype(&rc_engine_set_output_warp) set_warp = nullptr;
+    decltype(&rc_warp_curve) warp_curve = nullptr;
     decltype(&rc_host_alloc) alloc = nullptr;
     decltype(&rc_host_free) free = nullptr;
 };
@@ -232,6 +235,8 @@ static const FramesApi &frames_api() {
         a.set_time_map = (decltype(a.set_time_map))dlsym(RTLD_DEFAULT, "rc_engine_set_time_map");
         a.time_map_output_len = (decltype(a.time_map_output_len))dlsym(RTLD_DEFAULT, "rc_time_map_output_len");
         a.time_map_curve = (decltype(a.time_map_curve))dlsym(RTLD_DEFAULT, "rc_time_map_curve");
+        a.set_warp = (decltype(a.set_warp))dlsym(RTLD_DEFAULT, "rc_engine_set_output_warp");
+        a.warp_curve = (decltype(a.warp_curve))dlsym(RTLD_DEFAULT, "rc_warp_curve");
         a.alloc = (decltype(a.alloc))dlsym(RTLD_DEFAULT, "rc_host_alloc");
         a.free = (decltype(a.free))dlsym(RTLD_DEFAULT, "rc_host_free");
         if (!a.stretch || !a.alloc || !a.free) throw std::runtime_error("--frames-on-gpu: the engine library has no rc_engine_stretch_frames");
@@ -1151,6 +1156,9 @@ struct Opt {  // src/main.rs:27-122
     // factor is f at input time t (the duration grammar, behind -s / --autocrop), linear in between; --time-map: a file of
     // positions in input frames, one per line
     std::optional<std::string> factor_curve, time_map_file;
+    // not in the reference: a pitch that varies along the input (--frames-on-gpu; rc_engine_set_output_warp). --pitch-curve
+    // "t:c,t:c,...": the pitch is c cents at input time t, linear in cents in between
+    std::optional<std::string> pitch_curve;
     bool factor_given = false;
     std::optional<float> normalize;  // not in the reference: the output's peak is brought to this level on the GPU (--frames-on-gpu)
     // not in the reference (-p moves octaves, and decimates with no filter): pitch by any ratio and another output rate, by
@@ -1231,6 +1239,12 @@ void usage() {
             "                                       points; takes the place of -f (an explicit -f is refused). Under either map\n"
             "                                       flag --fade-output fades out into the map's last frame, and --pitch-ratio /\n"
             "                                       --pitch-cents are refused (they work through -f, which a map ignores)\n"
+            "        --pitch-curve <t:c,t:c,...>    With --frames-on-gpu: a pitch that varies along the input: c cents at input time t (a\n"
+            "                                       duration), linear in between, constant outside the points: a glide, a tape\n"
+            "                                       stop, a vibrato. The duration stays what -f or --factor-curve make it: the\n"
+            "                                       stretch runs at factor * ratio along a time map and the result is resampled on\n"
+            "                                       the GPU by a step that follows the curve. --output-rate composes; refused with\n"
+            "                                       --pitch-ratio, --pitch-cents and --time-map\n"
             "        --time-map <file>              With --frames-on-gpu: hop k reads the input at the k-th position of the file: one\n"
             "                                       integer (input frames) per line, # comments; positions may repeat (a hold),\n"
             "                                       decrease (reverse), be negative or lie past the end (silence)\n"
@@ -1362,6 +1376,7 @@ int run(int argc, char **argv) {
             o.factor_given = true;
         } else if (a == "--factor-curve") o.factor_curve = need(i);
         else if (a == "--time-map") o.time_map_file = need(i);
+        else if (a == "--pitch-curve") o.pitch_curve = need(i);
         else if (a == "-p" || a == "--pitch_multiple" || a == "--pitch-multiple") o.pitch_multiple = atoi(need(i).c_str());
         else if (a == "-a" || a == "--amplitude") o.amplitude = strtof(need(i).c_str(), nullptr);
         else if (a == "-i" || a == "--input") o.input = need(i);
@@ -1545,6 +1560,11 @@ int run(int argc, char **argv) {
     if (o.split_mono && !o.frames_on_gpu) throw std::runtime_error("--split-mono needs --frames-on-gpu");
     // (the map is state of the engine's whole-job calls: the streaming seam the host path runs on refuses one)
     if ((o.factor_curve || o.time_map_file) && !o.frames_on_gpu) throw std::runtime_error("--factor-curve / --time-map needs --frames-on-gpu");
+    if (o.pitch_curve && !o.frames_on_gpu) throw std::runtime_error("--pitch-curve needs --frames-on-gpu");
+    if (o.pitch_curve && o.pitch_ratio)
+        throw std::runtime_error("--pitch-curve cannot be combined with --pitch-ratio / --pitch-cents: one pitch, a constant or a curve");
+    if (o.pitch_curve && o.time_map_file)
+        throw std::runtime_error("--pitch-curve cannot be combined with --time-map: the curve builds the map itself (-f or --factor-curve set the speed)");
     if (o.factor_curve && o.time_map_file) throw std::runtime_error("--factor-curve cannot be combined with --time-map: one map");
     if (o.factor_curve && o.factor_given) throw std::runtime_error("--factor-curve takes the place of -f: give one of them");
     // (--pitch-ratio keeps the duration by stretching at factor * ratio: a map ignores the factor, so the two cannot compose)
@@ -1740,15 +1760,59 @@ int run(int argc, char **argv) {
             lap("autocrop");
         }
         size_t cap = rc_offline_output_len(&cfg, raw_count);
-        if (o.factor_curve || o.time_map_file) {
+        // --pitch-curve: (input frame, ratio) points, subdivided so that no segment spans more than 50 cents - linear in the
+        // ratio then stays within 0.2 cent of linear in cents
+        std::vector<double> pitch_at, pitch_ratio;
+        if (o.pitch_curve) {
+            if (!frames_api().set_warp || !frames_api().warp_curve)
+                throw std::runtime_error("--pitch-curve: the engine library has no rc_engine_set_output_warp");
+            std::vector<double> at, cents;
+            size_t b = 0;
+            for (;;) {
+                const size_t c = o.pitch_curve->find(',', b);
+                const std::string pt = o.pitch_curve->substr(b, c == std::string::npos ? c : c - b);
+                const size_t colon = pt.rfind(':');
+                uint64_t ms = 0;
+                char *end = nullptr;
+                const double v = colon == std::string::npos ? 0.0 : strtod(pt.c_str() + colon + 1, &end);
+                if (colon == std::string::npos || colon == 0 || !end || *end || end == pt.c_str() + colon + 1 || !std::isfinite(v) ||
+                    !parse_duration_ms(pt.substr(0, colon), &ms))
+                    throw std::runtime_error("--pitch-curve takes points t:c,t:c,... (t a duration, c cents), not " + pt);
+                at.push_back((double)ms / 1000.0 * (double)spec.sample_rate);
+                cents.push_back(v);
+                if (at.size() > 1 && !(at.back() > at[at.size() - 2])) throw std::runtime_error("--pitch-curve: times ascending, at " + pt);
+                if (c == std::string::npos) break;
+                b = c + 1;
+            }
+            for (size_t i = 0; i < at.size(); ++i) {
+                if (i) {
+                    const size_t parts = (size_t)std::ceil(std::fabs(cents[i] - cents[i - 1]) / 50.0);
+                    for (size_t k = 1; k < parts; ++k) {
+                        const double t = (double)k / (double)parts;
+                        pitch_at.push_back(at[i - 1] + (at[i] - at[i - 1]) * t);
+                        pitch_ratio.push_back(std::exp2((cents[i - 1] + (cents[i] - cents[i - 1]) * t) / 1200.0));
+                    }
+                }
+                pitch_at.push_back(at[i]);
+                pitch_ratio.push_back(std::exp2(cents[i] / 1200.0));
+            }
+            for (size_t i = 1; i < pitch_at.size(); ++i)
+                if (!(pitch_at[i] > pitch_at[i - 1])) throw std::runtime_error("--pitch-curve: two points too close in time for a curve this steep");
+        }
+        std::vector<int64_t> map_pos;  // the job's time map, where one is set
+        if (o.factor_curve || o.time_map_file || o.pitch_curve) {
             const FramesApi &api = frames_api();
             if (!api.set_time_map || !api.time_map_output_len || !api.time_map_curve)
-                throw std::runtime_error("--factor-curve / --time-map: the engine library has no rc_engine_set_time_map");
-            std::vector<int64_t> pos;
-            if (o.factor_curve) {  // "t:f,t:f,...": t in the duration grammar -> input frames, as duration_to_sample's product in doubles
+                throw std::runtime_error("--factor-curve / --time-map / --pitch-curve: the engine library has no rc_engine_set_time_map");
+            std::vector<int64_t> &pos = map_pos;
+            if (o.factor_curve || o.pitch_curve) {  // "t:f,t:f,...": t in the duration grammar -> input frames, as duration_to_sample's product in doubles
                 std::vector<double> at, fac;
                 size_t b = 0;
-                for (;;) {
+                if (!o.factor_curve) {  // -f: one point
+                    at.push_back(0.0);
+                    fac.push_back((double)o.factor);
+                }
+                for (; o.factor_curve;) {
                     const size_t c = o.factor_curve->find(',', b);
                     const std::string pt = o.factor_curve->substr(b, c == std::string::npos ? c : c - b);
                     const size_t colon = pt.rfind(':');
@@ -1763,6 +1827,25 @@ int run(int argc, char **argv) {
                     if (c == std::string::npos) break;
                     b = c + 1;
                 }
+                if (o.pitch_curve) {  // the product f(q) * r(q) at the union of the two curves' break points: the duration stays
+                    auto value = [](const std::vector<double> &x, const std::vector<double> &y, double q) {
+                        if (q <= x.front()) return y.front();
+                        if (q >= x.back()) return y.back();
+                        size_t i = 0;
+                        while (i + 2 < x.size() && x[i + 1] <= q) ++i;
+                        return y[i] + (y[i + 1] - y[i]) * ((q - x[i]) / (x[i + 1] - x[i]));
+                    };
+                    for (size_t i = 1; i < at.size(); ++i)
+                        if (!(at[i] > at[i - 1])) throw std::runtime_error("--factor-curve: times ascending and at least 0");
+                    std::vector<double> all(at);
+                    all.insert(all.end(), pitch_at.begin(), pitch_at.end());
+                    std::sort(all.begin(), all.end());
+                    all.erase(std::unique(all.begin(), all.end()), all.end());
+                    std::vector<double> prod;
+                    for (double q : all) prod.push_back(value(at, fac, q) * value(pitch_at, pitch_ratio, q));
+                    at.swap(all);
+                    fac.swap(prod);
+                }
                 size_t K = 0;
                 int rc = api.time_map_curve(&cfg, raw_count, at.data(), fac.data(), at.size(), nullptr, 0, &K);
                 if (rc == RC_ECAPACITY) {
@@ -1770,7 +1853,8 @@ int run(int argc, char **argv) {
                     rc = api.time_map_curve(&cfg, raw_count, at.data(), fac.data(), at.size(), pos.data(), K, &K);
                 }
                 if (rc != RC_OK)
-                    throw std::runtime_error("--factor-curve: times ascending and at least 0, factors in [2^-10, 2^20], at most 2^28 hops");
+                    throw std::runtime_error(std::string(o.factor_curve ? "--factor-curve" : "--pitch-curve") +
+                                             ": times ascending and at least 0, factors (times the pitch ratio) in [2^-10, 2^20], at most 2^28 hops");
             } else {
                 FILE *mf = fopen(o.time_map_file->c_str(), "r");
                 if (!mf) throw std::runtime_error("cannot open " + *o.time_map_file);
@@ -1802,7 +1886,37 @@ int run(int argc, char **argv) {
         }
         const uint32_t out_sb = pcm_sample_bytes(out_fmt);
         AudioSpec out_spec = spec;  // the output file's: --output-rate
-        if (o.pitch_ratio || o.output_rate) {
+        if (o.pitch_curve) {
+            // the warp: the curve's ratios along the map's hops, times rate_in / rate_out under --output-rate
+            const FramesApi &api = frames_api();
+            out_spec.sample_rate = o.output_rate.value_or(spec.sample_rate);
+            const double rate = (double)spec.sample_rate / (double)out_spec.sample_rate;
+            std::vector<double> ratio(pitch_ratio);
+            for (double &r : ratio) r *= rate;
+            for (double r : ratio)
+                if (!(r >= 0.125 && r <= 8.0)) throw std::runtime_error("--pitch-curve: the pitch ratio times rate_in / rate_out must lie in 1/8 ... 8");
+            size_t A = 0, n_out = 0;
+            std::vector<int64_t> anchor;
+            int rc = api.warp_curve(&cfg, map_pos.data(), map_pos.size(), pitch_at.data(), ratio.data(), ratio.size(), cap, nullptr, 0, &A, &n_out);
+            if (rc == RC_ECAPACITY) {
+                anchor.resize(A);
+                rc = api.warp_curve(&cfg, map_pos.data(), map_pos.size(), pitch_at.data(), ratio.data(), ratio.size(), cap, anchor.data(), A, &A, &n_out);
+            }
+            if (rc != RC_OK || anchor.size() < 2) throw std::runtime_error("--pitch-curve: no curve for this job (an empty result, or rows beyond 2^29 frames)");
+            if (api.set_warp(eng.h, anchor.data(), anchor.size(), n_out) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+            static const int64_t kTierD[RC_WARP_TIERS] = {RC_WARP_D_LIST};
+            int64_t d_lo = anchor[1] - anchor[0], d_hi = d_lo;
+            for (size_t k = 1; k + 1 < anchor.size(); ++k) d_lo = std::min(d_lo, anchor[k + 1] - anchor[k]), d_hi = std::max(d_hi, anchor[k + 1] - anchor[k]);
+            auto tier = [&](int64_t d) {
+                int t = 0;
+                while (d > kTierD[t]) ++t;
+                return t;
+            };
+            fprintf(stderr, "pitch curve: %zu hops, %zu frames out, ratios [%.6f, %.6f], tiers %d ... %d\n", map_pos.size(), n_out,
+                    std::ldexp((double)d_lo, -38), std::ldexp((double)d_hi, -38), tier(d_lo), tier(d_hi));
+            cap = n_out;
+            lap("pitch curve");
+        } else if (o.pitch_ratio || o.output_rate) {
             // one step for both: r input frames per output frame for the pitch, rate_in / rate_out for the rate
             const FramesApi &api = frames_api();
             if (!api.set_resample || !api.resample_ratio || !api.resample_len || !api.resample_table)
@@ -1827,7 +1941,7 @@ int run(int argc, char **argv) {
             size_t expected = (size_t)((float)raw_count * o.factor);
             if (out_spec.sample_rate != spec.sample_rate) expected = (size_t)((double)expected * (double)out_spec.sample_rate / (double)spec.sample_rate);
             // under a time map the job ends where the map ends, whatever -f says: the fade-out runs into the output's last frame
-            if (o.factor_curve || o.time_map_file) expected = cap;
+            if (o.factor_curve || o.time_map_file || o.pitch_curve) expected = cap;
             const bool in_fits = fade <= cap, out_fits = expected <= cap && expected >= fade;
             if (!in_fits) fprintf(stderr, "Fade in parameters out of bounds, ignoring.\n");
             if (!out_fits) fprintf(stderr, "Fade out parameters out of bounds, ignoring.\n");

@@ -7,7 +7,7 @@
 ROOT := ../../..
 CXX  ?= g++
 COMMON := -g -O1 -std=c++17 -Wall -fno-omit-frame-pointer rocoder_cli.cpp -ldl -lpthread
-all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../bin/engine_tsan ../../bin/engine_dk_asan ../../bin/engine_xch_asan ../../bin/engine_frames_asan ../../bin/engine_frames_pcm_asan ../../bin/engine_frames_norm_asan ../../bin/engine_frames_fade_asan ../../bin/engine_frames_power_asan ../../bin/engine_frames_map_asan ../../bin/engine_frames_dither_asan ../../bin/engine_frames_resample_asan ../../bin/engine_frames_limit_asan ../../bin/engine_frames_loud_asan ../../bin/engine_dk_sums_asan ../../bin/engine_dk_fb_asan ../../bin/engine_timemap_asan ../../bin/engine_timemap_tsan
+all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../bin/engine_tsan ../../bin/engine_dk_asan ../../bin/engine_xch_asan ../../bin/engine_frames_asan ../../bin/engine_frames_pcm_asan ../../bin/engine_frames_norm_asan ../../bin/engine_frames_fade_asan ../../bin/engine_frames_power_asan ../../bin/engine_frames_map_asan ../../bin/engine_frames_dither_asan ../../bin/engine_frames_resample_asan ../../bin/engine_frames_limit_asan ../../bin/engine_frames_loud_asan ../../bin/engine_dk_sums_asan ../../bin/engine_dk_fb_asan ../../bin/engine_timemap_asan ../../bin/engine_timemap_tsan ../../bin/engine_frames_warp_asan ../../bin/engine_frames_warp_tsan
 ../../bin/rocoder_asan: rocoder_cli.cpp $(ROOT)/include/rocoder_hip.h ../../librocoder_hip.so
 	mkdir -p ../../bin
 	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(COMMON) -o $@ -L../.. -lrocoder_hip \
@@ -25,11 +25,12 @@ ENGINE_FLAGS := -g -O1 -std=c++17 -Wall -Wno-unused-function -fno-omit-frame-poi
     -I/opt/rocm/include -x c++
 ASAN := -fsanitize=address,undefined -fno-sanitize-recover=undefined
 TSAN := -fsanitize=thread
-ENGINE_HDR := ../rc_kernels.h ../rc_long.h ../rc_frames.h ../rc_timemap.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h $(ROOT)/include/rocoder_hip_timemap.h
+ENGINE_HDR := ../rc_kernels.h ../rc_long.h ../rc_frames.h ../rc_timemap.h ../rc_warp.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h $(ROOT)/include/rocoder_hip_timemap.h \
+    $(ROOT)/include/rocoder_hip_warp.h
 # the engine and the stubs: compiled once per sanitizer, linked into every driver's program
 ENGINE_PARTS := rc_engine rc_rtc hip_stub hip_stub_long hip_stub_frames hip_stub_frames_pcm hip_stub_frames_norm \
     hip_stub_frames_fade hip_stub_frames_power hip_stub_frames_map hip_stub_frames_dither hip_stub_frames_resample hip_stub_frames_limit hip_stub_frames_loud hip_stub_rtc \
-    hip_stub_timemap rc_timemap_curve
+    hip_stub_timemap rc_timemap_curve hip_stub_frames_warp rc_warp_curve
 ENGINE_ASAN_OBJ := $(ENGINE_PARTS:%=../../bin/%.asan.o)
 ENGINE_TSAN_OBJ := $(ENGINE_PARTS:%=../../bin/%.tsan.o)
 vpath %.cpp .. $(ROOT)/tests/c
@@ -68,6 +69,10 @@ vpath %.cpp .. $(ROOT)/tests/c
 #                logs [t0, t1), src0 and src_len, reads every frame of its halo and writes a mark over its range)
 #   frames_loud  rc_engine_stretch_frames_loud and, with no engine, its host helpers (hip_stub_frames_loud.cpp's two measuring
 #                launchers read every frame and every parameter word the real ones read, log their rows and give fixed answers)
+#   frames_warp  rc_engine_set_output_warp on the four whole-job host-form entries, ASan + UBSan and TSan
+#                (hip_stub_frames_warp.cpp's launcher logs [m0, m1), src0, src_len and its last tap, holds the device anchors to
+#                the host's, reads every tap it may and writes a mark over its range; rc_warp_curve.cpp is built without
+#                contraction here too)
 #   dk_sums      a user device kernel with whole-hop sums loaded, over hip_stub_rtc_sums.cpp in place of hip_stub_rtc.cpp (it
 #                knows the second function, logs every lookup and launch, and its pass writes every row's sums)
 ENGINE_SUMS_ASAN_OBJ := $(filter-out ../../bin/hip_stub_rtc.asan.o,$(ENGINE_ASAN_OBJ)) ../../bin/hip_stub_rtc_sums.asan.o
@@ -84,6 +89,7 @@ ENGINE_FB_ASAN_OBJ := $(filter-out ../../bin/hip_stub_rtc.asan.o,$(ENGINE_ASAN_O
 #                CPU and logs its launches), over an engine built with -DRC_TEST_HOOKS=1 for rc_test_time_map_chunk_windows
 #                (rc_timemap_curve.cpp, a bit-exact host definition, is built without contraction here too)
 ../../bin/rc_timemap_curve.%.o: ENGINE_FLAGS += -ffp-contract=off
+../../bin/rc_warp_curve.%.o: ENGINE_FLAGS += -ffp-contract=off
 ../../bin/rc_engine.hooks.asan.o: ../rc_engine.cpp $(ENGINE_HDR)
 	mkdir -p ../../bin
 	$(CXX) $(ASAN) $(ENGINE_FLAGS) -DRC_TEST_HOOKS=1 -c $< -o $@

@@ -297,6 +297,49 @@ def resample_ratio(step: float):
     return int(num.value), int(den.value)
 
 
+def warp_table(tier: int) -> np.ndarray:
+    """The filter table of tier `tier` (0 ... 12) of an output warp (rc_warp_table; the definition is in
+    include/rocoder_hip_warp.h): float32 [257, T], row p the T = 2 W coefficients of phase p / 256. Pure host code."""
+    if not 0 <= int(tier) < 2 ** 32:
+        raise ValueError("tier is an unsigned 32-bit integer")
+    L = _lib.lib()
+    rows, taps = C.c_uint32(0), C.c_uint32(0)
+    check(L.rc_warp_table(int(tier), None, 0, C.byref(rows), C.byref(taps)), L)
+    out = np.empty((rows.value, taps.value), np.float32)
+    check(L.rc_warp_table(int(tier), _fp(out), out.size, C.byref(rows), C.byref(taps)), L)
+    return out
+
+
+def warp_curve(n: int, at, ratios, hop_pos=None, n_hops: Optional[int] = None, **kw):
+    """(anchors int64 [A], n_out): what `Engine.set_output_warp` takes for a pitch ratio that varies along the input of a
+    job whose rows have `n` frames (rc_warp_curve; the definition is in include/rocoder_hip_warp.h). The ratio is
+    `ratios[i]` (in [1/8, 8]) at input sample `at[i]`, linear in between and constant outside the points. `hop_pos` is
+    the job's time map, or None with `n_hops` for the engine's own grid k * sample_step_len. Pure host code."""
+    a = np.ascontiguousarray(at, np.float64).reshape(-1)
+    r = np.ascontiguousarray(ratios, np.float64).reshape(-1)
+    if a.size != r.size or a.size == 0:
+        raise ValueError("at and ratios hold the same number of points, at least one")
+    if not 0 <= int(n) < 2 ** 64:
+        raise ValueError("n is an unsigned integer")
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+    pos, pos_p = None, None
+    if hop_pos is not None:
+        pos = np.ascontiguousarray(hop_pos, np.int64).reshape(-1)
+        pos_p, n_hops = pos.ctypes.data_as(ip), pos.size
+    if n_hops is None or not 0 <= int(n_hops) < 2 ** 64:
+        raise ValueError("give hop_pos, or n_hops for the engine's grid")
+    cfg, _keep = make_config(**kw)
+    L = _lib.lib()
+    na, no = C.c_size_t(0), C.c_size_t(0)
+    args = (C.byref(cfg), pos_p, int(n_hops), a.ctypes.data_as(dp), r.ctypes.data_as(dp), a.size, int(n))
+    rc = L.rc_warp_curve(*args, None, 0, C.byref(na), C.byref(no))
+    if rc != _lib.RC_ECAPACITY:
+        check(rc, L)
+    out = np.empty(na.value, np.int64)
+    check(L.rc_warp_curve(*args, out.ctypes.data_as(ip), out.size, C.byref(na), C.byref(no)), L)
+    return out, int(no.value)
+
+
 def autocrop_points(bin_peak, bin_frames: int, n_frames: int, percentile: int = 30):
     """The reference's crop points (determine_noise_threshold + determine_autocrop_points, src/recorder.rs:165-191) from
     the peaks `Engine.frames_power` gives: (start, end) in frames - the job's frames [start, end) are what remains - or
@@ -379,6 +422,7 @@ class Engine:
         self._resample = None  # set_output_resample: (num, den) while a step is set
         self._limiter = False  # set_output_limiter: a limiter is set
         self._map_hops = None  # set_time_map: the hops of the map while one is set
+        self._warp_out = None  # set_output_warp: n_out while a warp is set
 
     def close(self):
         for o in list((getattr(self, "_views", None) or {}).values()):
@@ -488,6 +532,8 @@ class Engine:
     def _host_output_len(self, in_len: int) -> int:
         # what `stretch_host` and `stretch_frames` give: output_len, resampled where a step is set
         n = self.output_len(in_len)
+        if self._warp_out is not None:
+            return self._warp_out
         return n if self._resample is None else int(self._L.rc_resample_len(n, *self._resample))
 
     def stretch_host(self, channels_in, out: Optional[np.ndarray] = None) -> np.ndarray:
@@ -825,6 +871,27 @@ class Engine:
         self._check(self._L.rc_engine_set_output_resample(self._h, int(num), int(den)))
         self._resample = None if int(num) == int(den) else (int(num), int(den))
 
+    def set_output_warp(self, anchors=None, n_out: int = 0):
+        """Band-limited resampling of the result of `stretch_host` and `stretch_frames` on the GPU by a step that varies
+        along the output - a glide, a tape stop, a vibrato (rc_engine_set_output_warp; the definition is in
+        include/rocoder_hip_warp.h). `anchors` are int64 positions in the rows of the stretch result with 32 fractional
+        bits, one per block of 64 output frames and one behind the last; a block's step lies in [1/8, 8]. The result has
+        exactly `n_out` frames, and the fade, the limiter, the peak, the dither and the clipped count work on them.
+        `warp_curve` builds the anchors of a pitch curve. None (or an empty list) clears it. The alternative of
+        `set_output_resample`: each raises (RC_EINVAL) while the other is set, as bad anchors do, and the previous state
+        stays."""
+        if anchors is None or len(anchors) == 0:
+            self._check(self._L.rc_engine_set_output_warp(self._h, None, 0, 0))
+            self._warp_out = None
+            return
+        if any(not -2 ** 63 <= int(v) < 2 ** 63 for v in anchors):
+            raise ValueError("anchors are signed 64-bit integers")
+        if not 0 <= int(n_out) < 2 ** 64:
+            raise ValueError("n_out is an unsigned integer")
+        a = np.ascontiguousarray(anchors, np.int64).reshape(-1)
+        self._check(self._L.rc_engine_set_output_warp(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, int(n_out)))
+        self._warp_out = int(n_out)
+
     def set_output_limiter(self, drive: float = 1.0, ceiling: float = 0.0, lookahead: int = 0):
         """A look-ahead peak limiter on the result of `stretch_host` and `stretch_frames`, on the GPU, behind the resampler
         and the fade and in front of the peak of `normalize`, the dither and the quantiser (rc_engine_set_output_limiter;
@@ -1127,4 +1194,4 @@ def stretch(channels_in, window_len=16384, factor=1.0, amplitude=1.0, pitch_mult
 
 __all__ = ["AudioSpec", "AudioBus", "Engine", "ReFFT", "Stretcher", "StretcherProcessor", "stretch",
            "derive_params", "offline_output_len", "load_kernel_library", "RocoderError", "compile_device_kernel",
-           "DeviceKernelCompileError", "time_map_output_len", "time_map_curve"]
+           "DeviceKernelCompileError", "time_map_output_len", "time_map_curve", "warp_table", "warp_curve"]
