@@ -793,6 +793,9 @@ int rc_calib_valu(int device, void *hip_stream, uint32_t launches, float *ms_per
 /* ---- output warp: rc_engine_set_output_warp, rc_warp_table, rc_warp_curve ---------------------- */
 #include "rocoder_hip_warp.h"
 
+/* ---- mix bus: rc_bus_*, rc_engine_mix_frames, rc_engine_bus_frames, rc_mix_envelope ------------ */
+#include "rocoder_hip_mix.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,6 +181,22 @@ WARP_SYMBOLS = {
                                 C.POINTER(C.c_int64), _sz, C.POINTER(_sz), C.POINTER(_sz)]),
 }
 
+# ... and every symbol include/rocoder_hip_mix.h declares (rocoder_hip.h includes it)
+_bus = C.c_void_p
+MIX_SYMBOLS = {
+    "rc_bus_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, C.POINTER(_bus)]),
+    "rc_bus_destroy": (None, [_bus]),
+    "rc_bus_clear": (C.c_int, [_bus]),
+    "rc_bus_info": (C.c_int, [_bus, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "rc_bus_device_rows": (C.c_int, [_bus, C.POINTER(_fp), C.POINTER(_sz)]),
+    "rc_engine_mix_frames": (C.c_int, [_eng, C.c_void_p, _sz, C.c_uint32, _bus, C.c_int64, C.POINTER(C.c_uint64), _fp, _sz, _fp,
+                                       C.POINTER(C.c_uint64)]),
+    "rc_engine_bus_frames": (C.c_int, [_eng, _bus, C.c_void_p, _sz, C.c_uint32, C.c_float, C.POINTER(_sz), _fp, _fp,
+                                       C.POINTER(C.c_uint64)]),
+    "rc_mix_envelope": (C.c_int, [C.POINTER(C.c_uint64), _fp, _sz, C.c_uint64, _sz, _fp]),
+}
+RC_MIX_MAX_KEYS = 4096
+
 _lib = None
 
 
@@ -204,7 +220,7 @@ def _load(path: str) -> C.CDLL:
     except ImportError:
         pass
     L = C.CDLL(path)
-    for name, (res, args) in list(SYMBOLS.items()) + list(TIME_MAP_SYMBOLS.items()) + list(WARP_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(TIME_MAP_SYMBOLS.items()) + list(WARP_SYMBOLS.items()) + list(MIX_SYMBOLS.items()):
         fn = getattr(L, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

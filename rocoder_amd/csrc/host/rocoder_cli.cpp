@@ -209,6 +209,11 @@ struct FramesApi {
     // (--pitch-curve only: may be missing, both or neither)
     decltype(&rc_engine_set_output_warp) set_warp = nullptr;
     decltype(&rc_warp_curve) warp_curve = nullptr;
+    // (--layer only: may be missing, all or none)
+    decltype(&rc_bus_create) bus_create = nullptr;
+    decltype(&rc_bus_destroy) bus_destroy = nullptr;
+    decltype(&rc_engine_mix_frames) mix_frames = nullptr;
+    decltype(&rc_engine_bus_frames) bus_frames = nullptr;
     decltype(&rc_host_alloc) alloc = nullptr;
     decltype(&rc_host_free) free = nullptr;
 };
@@ -237,6 +242,10 @@ static const FramesApi &frames_api() {
         a.time_map_curve = (decltype(a.time_map_curve))dlsym(RTLD_DEFAULT, "rc_time_map_curve");
         a.set_warp = (decltype(a.set_warp))dlsym(RTLD_DEFAULT, "rc_engine_set_output_warp");
         a.warp_curve = (decltype(a.warp_curve))dlsym(RTLD_DEFAULT, "rc_warp_curve");
+        a.bus_create = (decltype(a.bus_create))dlsym(RTLD_DEFAULT, "rc_bus_create");
+        a.bus_destroy = (decltype(a.bus_destroy))dlsym(RTLD_DEFAULT, "rc_bus_destroy");
+        a.mix_frames = (decltype(a.mix_frames))dlsym(RTLD_DEFAULT, "rc_engine_mix_frames");
+        a.bus_frames = (decltype(a.bus_frames))dlsym(RTLD_DEFAULT, "rc_engine_bus_frames");
         a.alloc = (decltype(a.alloc))dlsym(RTLD_DEFAULT, "rc_host_alloc");
         a.free = (decltype(a.free))dlsym(RTLD_DEFAULT, "rc_host_free");
         if (!a.stretch || !a.alloc || !a.free) throw std::runtime_error("--frames-on-gpu: the engine library has no rc_engine_stretch_frames");
@@ -1180,7 +1189,100 @@ struct Opt {  // src/main.rs:27-122
     uint32_t dither = RC_DITHER_NONE;
     bool dither_given = false;
     std::optional<uint64_t> dither_seed;  // [default: --seed]
+    // not in the reference's CLI (its mixer, src/mixer.rs, serves playback): --layer SPEC, repeatable. With one or more the run
+    // is a mix on the GPU (--frames-on-gpu, -o): every SPEC is one layer over the same input file, the main flags are the
+    // defaults of every layer and the output chain of the sum (rc_engine_mix_frames / rc_engine_bus_frames)
+    std::vector<std::string> layers;
 };
+
+// one --layer SPEC: key=value,... over the defaults the main flags give
+struct LayerSpec {
+    float factor = 1.0f, amplitude = 1.0f, gain = 1.0f;
+    int pitch_multiple = 1;
+    std::optional<double> ratio;  // cents, as --pitch-cents
+    uint64_t seed = 0, at_ms = 0;
+    std::optional<uint64_t> fade_ms;
+};
+
+LayerSpec parse_layer(const std::string &spec, const LayerSpec &defaults) {
+    LayerSpec l = defaults;
+    size_t b = 0;
+    while (b <= spec.size()) {
+        const size_t c = spec.find(',', b);
+        const std::string kv = spec.substr(b, c == std::string::npos ? c : c - b);
+        b = c == std::string::npos ? spec.size() + 1 : c + 1;
+        if (kv.empty() && spec.empty()) break;  // (an empty SPEC: the defaults)
+        const size_t eq = kv.find('=');
+        const std::string k = kv.substr(0, eq), v = eq == std::string::npos ? "" : kv.substr(eq + 1);
+        char *end = nullptr;
+        auto bad = [&]() { return std::runtime_error("--layer: bad " + kv + " in " + spec + " (keys: f, p, cents, a, seed, gain, at, fade)"); };
+        if (eq == std::string::npos || v.empty()) throw bad();
+        if (k == "f") {
+            l.factor = strtof(v.c_str(), &end);
+            if (*end) throw bad();
+        } else if (k == "p") {
+            l.pitch_multiple = (int)strtol(v.c_str(), &end, 10);
+            if (*end) throw bad();
+        } else if (k == "a") {
+            l.amplitude = strtof(v.c_str(), &end);
+            if (*end) throw bad();
+        } else if (k == "cents") {
+            const double r = std::exp2(strtod(v.c_str(), &end) / 1200.0);
+            if (*end || !(r >= 0.125 && r <= 8.0)) throw bad();
+            l.ratio = r;
+        } else if (k == "seed") {
+            l.seed = strtoull(v.c_str(), &end, 0);
+            if (*end) throw bad();
+        } else if (k == "gain") {  // linear, or with a trailing dB
+            float g = strtof(v.c_str(), &end);
+            const bool db = end != v.c_str() && (std::string(end) == "dB" || std::string(end) == "db");
+            if (db) g = (float)std::pow(10.0, (double)g / 20.0);
+            if (end == v.c_str() || (*end && !db) || !std::isfinite(g)) throw bad();
+            l.gain = g;
+        } else if (k == "at" || k == "fade") {
+            uint64_t ms = 0;
+            if (!parse_duration_ms(v, &ms)) throw bad();
+            if (k == "at") l.at_ms = ms;
+            else l.fade_ms = ms;
+        } else {
+            throw bad();
+        }
+    }
+    return l;
+}
+
+// The keys of Layer::fade_in_out (src/mixer.rs:179-190), placed as dur_to_sample places them: (0, 0), (d(fade), 1),
+// (d(T - fade), 1), (d(T), 0), T the reference's expected_total_samples as a Duration of f32 seconds; durations are whole
+// nanoseconds, as the reference's are. Every amplitude is scaled by the layer's gain. A key that repeats the frame and
+// amplitude of the one before it is dropped; a repeated frame with another amplitude is refused. Without a fade: one key
+// that holds the gain, or none at gain 1.
+void layer_keys(const LayerSpec &l, size_t expected_total, uint32_t rate, std::vector<uint64_t> *kf, std::vector<float> *ka) {
+    kf->clear();
+    ka->clear();
+    if (!l.fade_ms) {
+        if (l.gain != 1.0f) {
+            kf->push_back(0);
+            ka->push_back(l.gain);
+        }
+        return;
+    }
+    auto d = [&](uint64_t ns) {  // dur_to_sample(Duration): (dur.as_secs_f32() * rate as f32) as usize
+        const float secs = (float)(ns / 1000000000ull) + (float)(ns % 1000000000ull) / 1e9f;
+        return (uint64_t)(secs * (float)rate);
+    };
+    const uint64_t F = *l.fade_ms * 1000000ull;
+    const uint64_t T = (uint64_t)((double)((float)expected_total / (float)rate) * 1e9);  // Duration::from_secs_f32
+    if (F > T) throw std::runtime_error("--layer: a fade of " + std::to_string(*l.fade_ms) + " ms is longer than the layer");
+    const uint64_t frames[4] = {0, d(F), d(T - F), d(T)};
+    const float amps[4] = {0.0f, l.gain, l.gain, 0.0f};
+    for (int i = 0; i < 4; ++i) {
+        if (!kf->empty() && kf->back() == frames[i] && ka->back() == amps[i]) continue;
+        if (!kf->empty() && kf->back() >= frames[i])
+            throw std::runtime_error("--layer: the fade's keys meet at frame " + std::to_string(frames[i]) + " with two amplitudes");
+        kf->push_back(frames[i]);
+        ka->push_back(amps[i]);
+    }
+}
 
 void usage() {
     fprintf(stderr,
@@ -1197,6 +1299,11 @@ void usage() {
             "    -b, --buffer <buffer-dur>          The maximum amount of audio to process ahead of time [default: 1]\n"
             "    -d, --duration <duration>          Duration to use from input audio (hh:mm:ss.ss)\n"
             "    -x, --fade <fade>                  Fade (playback only; ignored with -o unless --fade-output is given) [default: 1]\n"
+            "        --layer <key=value,...>        With --frames-on-gpu and -o, repeatable: the run is a mix of one layer per --layer over\n"
+            "                                       the same input, summed on the GPU. Keys: f, p, cents, a, seed (defaults: the main\n"
+            "                                       flags), gain (linear or dB), at (the layer's offset in the output), fade (the\n"
+            "                                       reference's fade_in_out keys; the fade-out is cut where the layer ends). The main\n"
+            "                                       flags' --fade-output, --limit*, --normalize, --dither*, --output-format act on the sum\n"
             "        --fade-output                  With --frames-on-gpu: fade the output file in and out over -x, as the\n"
             "                                       reference fades its playback, on the GPU in front of --normalize and the\n"
             "                                       quantiser; a fade longer than the output is left out with a warning\n"
@@ -1383,6 +1490,7 @@ int run(int argc, char **argv) {
         else if (a == "--rotate-channels") o.rotate_channels = true;
         else if (a == "--frames-on-gpu") o.frames_on_gpu = true;
         else if (a == "--fade-output") o.fade_output = true;
+        else if (a == "--layer") o.layers.push_back(need(i));
         else if (a == "--autocrop") o.autocrop = true;
         else if (a == "--split-mono") o.split_mono = true;
         else if (a == "--channel-map") {
@@ -1570,6 +1678,13 @@ int run(int argc, char **argv) {
     // (--pitch-ratio keeps the duration by stretching at factor * ratio: a map ignores the factor, so the two cannot compose)
     if ((o.factor_curve || o.time_map_file) && o.pitch_ratio)
         throw std::runtime_error("--pitch-ratio / --pitch-cents cannot be combined with --factor-curve / --time-map: a map sets the speed, not -f");
+    if (!o.layers.empty()) {
+        if (!o.frames_on_gpu || !o.output) throw std::runtime_error("--layer needs --frames-on-gpu and -o");
+        const char *with = o.loudness || o.true_peak ? "--loudness" : o.pitch_curve ? "--pitch-curve" : o.factor_curve ? "--factor-curve"
+                           : o.time_map_file ? "--time-map" : o.device_kernel_src ? "--device-kernel-src" : o.output_rate ? "--output-rate"
+                           : o.channel_map ? "--channel-map" : o.split_mono ? "--split-mono" : nullptr;
+        if (with) throw std::runtime_error(std::string("--layer cannot be combined with ") + with);
+    }
     if (o.dither_seed && !o.dither_given) throw std::runtime_error("--dither-seed needs --dither");
     // dither belongs in front of a quantiser of 8, 16 or 24 bits: f32 has none, and a step of i32 lies below an f32's precision
     auto check_dither_format = [&](uint32_t fmt) {
@@ -1758,6 +1873,129 @@ int run(int argc, char **argv) {
             }
             clip_raw();
             lap("autocrop");
+        }
+        // "<path>.part" first, as WavStreamWriter: a failed run leaves no output file
+        auto write_output = [&](const unsigned char *frames, size_t n, const AudioSpec &out_spec, uint64_t clipped) {
+            const uint32_t sb = pcm_sample_bytes(out_fmt);
+            const std::string tmp = *o.output + ".part";
+            FILE *g = fopen(tmp.c_str(), "wb");
+            if (!g) throw std::runtime_error("cannot create " + tmp);
+            write_wav_header(g, out_spec, n, out_fmt);
+            const size_t total = n * spec.channels;
+            const bool ok = fwrite(frames, sb, total, g) == total && write_wav_pad(g, out_spec, n, out_fmt);
+            if (fclose(g) != 0 || !ok) {
+                (void)std::remove(tmp.c_str());
+                throw std::runtime_error("write failed (disk full?)");
+            }
+            if (std::rename(tmp.c_str(), o.output->c_str()) != 0) {
+                (void)std::remove(tmp.c_str());
+                throw std::runtime_error("cannot move " + tmp + " to " + *o.output);
+            }
+            lap("write output");
+            report_clipped(clipped, total);
+        };
+        if (!o.layers.empty()) {
+            // A mix: every --layer is one frames job over the same input, accumulated into a device-resident bus
+            // under its keys; the main job is no layer, its engine is the master that sends the bus through the main flags'
+            // output chain (--fade-output, --limit*, --normalize, --dither*, --output-format)
+            const FramesApi &api = frames_api();
+            if (!api.bus_create || !api.bus_destroy || !api.mix_frames || !api.bus_frames)
+                throw std::runtime_error("--layer: the engine library has no rc_engine_mix_frames");
+            LayerSpec defaults;
+            defaults.factor = o.factor;
+            defaults.amplitude = o.amplitude;
+            defaults.pitch_multiple = o.pitch_multiple;
+            defaults.ratio = o.pitch_ratio;
+            defaults.seed = o.seed;
+            struct Planned {
+                LayerSpec l;
+                rc_config cfg;
+                uint32_t num = 1, den = 1;
+                size_t n = 0;
+                int64_t offset = 0;
+                std::vector<uint64_t> kf;
+                std::vector<float> ka;
+            };
+            std::vector<Planned> plan;
+            size_t N = 0;
+            for (const std::string &s : o.layers) {
+                Planned p;
+                p.l = parse_layer(s, defaults);
+                p.cfg = cfg;
+                p.cfg.factor = p.l.ratio ? (float)((double)p.l.factor * *p.l.ratio) : p.l.factor;  // (as --pitch-cents: the duration stays f * L)
+                p.cfg.amplitude = p.l.amplitude;
+                p.cfg.pitch_multiple = p.l.pitch_multiple;
+                p.cfg.seed = p.l.seed;
+                p.n = rc_offline_output_len(&p.cfg, raw_count);
+                if (p.l.ratio) {
+                    if (!api.set_resample || !api.resample_ratio || !api.resample_len) throw std::runtime_error("--layer cents: the engine library has no rc_engine_set_output_resample");
+                    if (api.resample_ratio((float)*p.l.ratio, &p.num, &p.den) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+                    if (p.num != p.den) p.n = api.resample_len(p.n, p.num, p.den);
+                }
+                p.offset = (int64_t)((float)((double)p.l.at_ms / 1000.0) * (float)spec.sample_rate);  // duration_to_sample
+                layer_keys(p.l, (size_t)((float)raw_count * p.l.factor), spec.sample_rate, &p.kf, &p.ka);
+                N = std::max(N, (size_t)p.offset + p.n);
+                plan.push_back(std::move(p));
+            }
+            rc_bus *bus = nullptr;
+            if (api.bus_create(o.device, spec.channels, N, &bus) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+            struct BusGuard {
+                rc_bus *b;
+                ~BusGuard() { frames_api().bus_destroy(b); }
+            } bus_guard{bus};
+            fprintf(stderr, "mix: %zu layers, %zu frames\n", plan.size(), N);
+            const size_t frame_bytes = (size_t)spec.channels * raw.sample_bytes;
+            for (size_t i = 0; i < plan.size(); ++i) {
+                const Planned &p = plan[i];
+                Engine layer;  // (one at a time: a layer's rows are freed before the next engine allocates its own)
+                if (rc_engine_create(&p.cfg, &layer.h) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+                if (p.l.ratio && api.set_resample(layer.h, p.num, p.den) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+                uint64_t mixed = 0;
+                if (api.mix_frames(layer.h, raw.data.p + raw_first * frame_bytes, raw_count, raw.format, bus, p.offset, p.kf.data(), p.ka.data(),
+                                   p.kf.size(), nullptr, &mixed) != RC_OK)
+                    throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+                fprintf(stderr, "layer %zu: factor %.9g, ratio %u/%u, offset %lld, %llu frames mixed\n", i, (double)p.l.factor, p.num, p.den,
+                        (long long)p.offset, (unsigned long long)mixed);
+            }
+            lap("mix layers");
+            if (o.fade_output) {  // the main job's fade, on the sum: in over the first F frames, out over the last F
+                if (!api.set_fade) throw std::runtime_error("--fade-output: the engine library has no rc_engine_set_output_fade");
+                const size_t fade = (size_t)((float)((double)o.fade_ms / 1000.0) * (float)spec.sample_rate);
+                const bool fits = fade <= N;
+                if (!fits) fprintf(stderr, "Fade in parameters out of bounds, ignoring.\nFade out parameters out of bounds, ignoring.\n");
+                if (api.set_fade(eng.h, fits ? fade : 0, fits ? N - fade : RC_FADE_NONE, fits ? fade : 0) != RC_OK)
+                    throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+                if (fits) fprintf(stderr, "fade in %zu frames, out from %zu over %zu\n", fade, N - fade, fade);
+            }
+            if (o.limit) {
+                if (!api.set_limiter || !api.limiter_stats) throw std::runtime_error("--limit: the engine library has no rc_engine_set_output_limiter");
+                const size_t look = (size_t)((float)((double)o.limit_lookahead_ms / 1000.0) * (float)spec.sample_rate);
+                if (look > RC_LIMITER_MAX_LOOKAHEAD)
+                    throw std::runtime_error("--limit-lookahead is " + std::to_string(look) + " frames at " + std::to_string(spec.sample_rate) +
+                                             " Hz, at most " + std::to_string(RC_LIMITER_MAX_LOOKAHEAD));
+                if (api.set_limiter(eng.h, o.limit_drive, *o.limit, (uint32_t)look) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+            }
+            if (o.dither != RC_DITHER_NONE) {
+                if (!api.set_dither) throw std::runtime_error("--dither: the engine library has no rc_engine_set_output_dither");
+                if (api.set_dither(eng.h, o.dither, o.dither_seed.value_or(o.seed)) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+            }
+            PinnedBytes out(N * spec.channels * pcm_sample_bytes(out_fmt));
+            size_t n = 0;
+            uint64_t clipped = 0;
+            float peak = 0.0f, gain = 1.0f;
+            if (api.bus_frames(eng.h, bus, out.p, N, out_fmt, o.normalize.value_or(0.0f), &n, &peak, &gain, &clipped) != RC_OK)
+                throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+            lap("master");
+            if (o.normalize) fprintf(stderr, "peak %.9g, gain %.9g\n", (double)peak, (double)gain);
+            if (o.limit) {
+                float min_gain = 1.0f;
+                uint64_t limited = 0;
+                if (api.limiter_stats(eng.h, &min_gain, &limited) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+                fprintf(stderr, "limited %llu of %zu frames, lowest gain %.9g (%.1f dB)\n", (unsigned long long)limited, n, (double)min_gain,
+                        min_gain > 0.0f ? 20.0 * std::log10((double)min_gain) : -INFINITY);
+            }
+            write_output(out.p, n, spec, clipped);
+            return 0;
         }
         size_t cap = rc_offline_output_len(&cfg, raw_count);
         // --pitch-curve: (input frame, ratio) points, subdivided so that no segment spans more than 50 cents - linear in the
@@ -2000,23 +2238,7 @@ int run(int argc, char **argv) {
             fprintf(stderr, "limited %llu of %zu frames, lowest gain %.9g (%.1f dB)\n", (unsigned long long)limited, n, (double)min_gain,
                     min_gain > 0.0f ? 20.0 * std::log10((double)min_gain) : -INFINITY);
         }
-        // "<path>.part" first, as WavStreamWriter: a failed run leaves no output file
-        const std::string tmp = *o.output + ".part";
-        FILE *g = fopen(tmp.c_str(), "wb");
-        if (!g) throw std::runtime_error("cannot create " + tmp);
-        write_wav_header(g, out_spec, n, out_fmt);
-        const size_t total = n * spec.channels;
-        const bool ok = fwrite(out.p, out_sb, total, g) == total && write_wav_pad(g, out_spec, n, out_fmt);
-        if (fclose(g) != 0 || !ok) {
-            (void)std::remove(tmp.c_str());
-            throw std::runtime_error("write failed (disk full?)");
-        }
-        if (std::rename(tmp.c_str(), o.output->c_str()) != 0) {
-            (void)std::remove(tmp.c_str());
-            throw std::runtime_error("cannot move " + tmp + " to " + *o.output);
-        }
-        lap("write output");
-        report_clipped(clipped, total);
+        write_output(out.p, n, out_spec, clipped);
         return 0;
     }
     const HostDither host_dither(o.dither, o.dither_seed.value_or(o.seed), spec.channels);  // the writers' quantiser below

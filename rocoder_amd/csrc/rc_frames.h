@@ -355,6 +355,37 @@ struct FramesTruePeakParams {
     FramesNormWords *norm;
 };
 
+// The mix launch (rc_engine_mix_frames; the definition is stated in include/rocoder_hip_mix.h), from a layer's planar rows
+// into the bus rows. `rows` is the sample of the layer's first channel at layer frame t0 (rows `stride` floats apart,
+// `channels` = CL of them); the launch covers the layer frames [t0, t1). `bus` is frame 0 of the first bus row (16-byte
+// aligned; rows bus_stride floats apart, a multiple of 4; bus_channels = CB rows of bus_frames = N frames). For every t of
+// the range with 0 <= u = offset + t < N and every cb:
+//   bus[cb][u] = bus[cb][u] + s[cb][t] * amp(t)      one multiplication, then one addition, never one fma
+//   s[cb][t]   = x[cb][t] where send is null (CL == CB), else ONE chain acc = fmaf(send[cb * CL + cl], x[cl][t], acc) from +0
+//   amp(t)     = the envelope of the keys (key_frame, key_amp: device tables of n_keys entries) on the layer's clock
+// and no other word of the bus is read or written; frames that fall outside the bus are dropped, and nothing is launched
+// for a range that falls wholly outside. A sample's bits do not depend on the launch, the tile or the range. The launcher
+// refuses (hipErrorInvalidValue, nothing launched) t1 < t0, n_keys > kMixMaxKeys, and with a non-empty range a null
+// pointer (send may be null), a null send with CL != CB, a bus that is not aligned as stated, |offset|, t1 or N above 2^62.
+constexpr uint32_t kMixMaxKeys = 4096;  // RC_MIX_MAX_KEYS
+struct FramesMixParams {
+    const float *rows;
+    uint64_t stride;
+    uint32_t channels;
+    uint64_t t0, t1;
+    float *bus;
+    uint64_t bus_stride;
+    uint32_t bus_channels;
+    uint64_t bus_frames;
+    int64_t offset;
+    const uint64_t *key_frame;
+    const float *key_amp;
+    uint32_t n_keys;
+    const float *send;
+};
+// nullptr where the keys are what rc_engine_mix_frames accepts, else what is wrong with them (rc_mix_envelope.cpp; host code)
+const char *mix_check_keys(const uint64_t *key_frame, const float *key_amp, size_t n_keys);
+
 // (all: nothing is launched for n_frames == 0; a job of more than 2^27 frames goes out as several launches)
 hipError_t launch_frames_unpack(uint32_t format, const FramesUnpackParams &p, hipStream_t s);
 hipError_t launch_frames_pack(const FramesPackParams &p, hipStream_t s);
@@ -372,5 +403,6 @@ hipError_t launch_frames_limit(const FramesLimitParams &p, hipStream_t s);      
 inline uint64_t frames_limit_scratch_words(uint64_t /*frames*/, uint32_t /*L*/) { return 0; }
 hipError_t launch_frames_loud_energy(const FramesLoudEnergyParams &p, hipStream_t s);  // (rc_frames_loud.hip)
 hipError_t launch_frames_true_peak(const FramesTruePeakParams &p, hipStream_t s);      // (rc_frames_loud.hip)
+hipError_t launch_frames_mix(const FramesMixParams &p, hipStream_t s);                 // (rc_frames_mix.hip; one launch whatever the range)
 
 }  // namespace rc

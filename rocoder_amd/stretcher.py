@@ -340,6 +340,76 @@ def warp_curve(n: int, at, ratios, hop_pos=None, n_hops: Optional[int] = None, *
     return out, int(no.value)
 
 
+def _mix_keys(keys):
+    """keys: None or a sequence of (frame, amp) -> (uint64 frames, float32 amps)."""
+    if keys is None or len(keys) == 0:
+        return np.zeros(0, np.uint64), np.zeros(0, np.float32)
+    for k in keys:
+        if len(k) != 2 or not 0 <= int(k[0]) < 2 ** 64:
+            raise ValueError("keys is a sequence of (frame, amp), frame an unsigned integer")
+    kf = np.array([int(k[0]) for k in keys], np.uint64)
+    with np.errstate(over="ignore"):
+        ka = np.array([k[1] for k in keys], np.float32)
+    return kf, ka
+
+
+def mix_envelope(keys, t0: int, n: int) -> np.ndarray:
+    """amp(t0 + i), i < n: the keyframed envelope of a mix layer (rc_mix_envelope; the definition - the reference's
+    math::sqrt_interp between the keys, the first and the last amplitude outside them - is in include/rocoder_hip_mix.h).
+    `keys` is a sequence of (frame, amp) with strictly increasing frames. Pure host code."""
+    kf, ka = _mix_keys(keys)
+    if not (0 <= int(t0) < 2 ** 64 and 0 <= int(n) < 2 ** 63):
+        raise ValueError("t0 and n are unsigned integers")
+    out = np.empty(int(n), np.float32)
+    L = _lib.lib()
+    check(L.rc_mix_envelope(kf.ctypes.data_as(C.POINTER(C.c_uint64)), _fp(ka), kf.size, int(t0), int(n), _fp(out)), L)
+    return out
+
+
+class Bus:
+    """A device-resident mix bus (rc_bus): `channels` planar float32 rows of `n_frames` frames on `device`, all zero when
+    created and after `clear()`. `Engine.mix_frames` accumulates layers into it, `Engine.bus_frames` reads it out through an
+    engine's master stages."""
+
+    def __init__(self, channels: int, n_frames: int, device: int = 0):
+        if not (0 <= int(channels) < 2 ** 32 and 0 <= int(n_frames) < 2 ** 64):
+            raise ValueError("channels and n_frames are unsigned integers")
+        self._L = _lib.lib()
+        h = C.c_void_p()
+        check(self._L.rc_bus_create(int(device), int(channels), int(n_frames), C.byref(h)), self._L)
+        self._h = h
+        self.channels, self.n_frames, self.device = int(channels), int(n_frames), int(device)
+
+    @property
+    def layers(self) -> int:
+        n = C.c_uint32(0)
+        check(self._L.rc_bus_info(self._h, None, None, C.byref(n)), self._L)
+        return int(n.value)
+
+    def clear(self):
+        check(self._L.rc_bus_clear(self._h), self._L)
+
+    def device_rows(self):
+        """(device address of row 0, row stride in floats): for device callers."""
+        p, stride = C.POINTER(C.c_float)(), C.c_size_t(0)
+        check(self._L.rc_bus_device_rows(self._h, C.byref(p), C.byref(stride)), self._L)
+        return C.cast(p, C.c_void_p).value or 0, int(stride.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.rc_bus_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 def autocrop_points(bin_peak, bin_frames: int, n_frames: int, percentile: int = 30):
     """The reference's crop points (determine_noise_threshold + determine_autocrop_points, src/recorder.rs:165-191) from
     the peaks `Engine.frames_power` gives: (start, end) in frames - the job's frames [start, end) are what remains - or
@@ -665,6 +735,64 @@ class Engine:
         assert got.value == n_out
         self._read_limiter_stats()
         return out[:n_out]
+
+    def mix_frames(self, frames, bus: "Bus", offset: int = 0, keys=None, send=None, fmt: Optional[str] = None) -> int:
+        """One layer of a mix (rc_engine_mix_frames): the job `stretch_frames(frames, fmt)` would run under the engine's
+        current state, with its planar float32 result accumulated on the GPU into `bus` instead of being downloaded:
+        bus[cb][offset + t] += s[cb][t] * amp(t). `keys` is a sequence of (frame, amp) on the layer's own clock
+        (`mix_envelope`; None: 1), `send` a [bus.channels, self.channels] matrix (None: the channels as they are, which
+        needs equal counts). Frames that fall outside the bus are dropped; returns the number that landed. The call
+        blocks: layers are summed in call order."""
+        raw, code, n = self._raw_frames(frames, fmt)
+        kf, ka = _mix_keys(keys)
+        send_p = None
+        if send is not None:
+            with np.errstate(over="ignore"):
+                send_a = np.ascontiguousarray(send, np.float32)
+            if send_a.shape != (bus.channels, self.channels):
+                raise ValueError(f"send must be [{bus.channels}, {self.channels}]")
+            send_p = _fp(send_a)
+        if not -2 ** 63 <= int(offset) < 2 ** 63:
+            raise ValueError("offset is a signed 64-bit integer")
+        mixed = C.c_uint64(0)
+        src = C.c_void_p(raw.ctypes.data) if raw.size else None
+        self._check(self._L.rc_engine_mix_frames(self._h, src, n, code, bus._h, int(offset), kf.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 _fp(ka), kf.size, send_p, C.byref(mixed)))
+        self._read_limiter_stats()
+        return int(mixed.value)
+
+    def bus_frames(self, bus: "Bus", out_format: str = "f32", target_peak: Optional[float] = None, out: Optional[np.ndarray] = None):
+        """The master of a mix (rc_engine_bus_frames): the rows of `bus` through this engine's output fade, limiter, peak
+        normalisation (`target_peak`, None: none), dither and quantiser into interleaved frames of `out_format`. No hops
+        run: the channel map, time map, resampler, warp and device kernels do not apply. The bus is not changed. Returns
+        (frames, stats): what `stretch_frames(out_fmt=out_format)` returns for that format, [bus.n_frames, channels], and
+        {"peak", "gain", "clipped"} (also in `last_peak`, `last_gain`, `last_clipped`)."""
+        if out_format not in _lib.PCM_FORMATS:
+            raise ValueError(f"out_format must be one of {sorted(_lib.PCM_FORMATS)}")
+        tp = 0.0
+        if target_peak is not None:
+            with np.errstate(over="ignore"):
+                tp = float(np.float32(target_peak))
+            if not (tp > 0 and np.isfinite(tp)):
+                raise ValueError("target_peak must be a finite float32 above 0")
+        ocode = _lib.PCM_FORMATS[out_format]
+        dtype, tail = {"u8": (np.uint8, ()), "i16": ("<i2", ()), "i24": (np.uint8, (3,)), "i32": ("<i4", ()), "f32": ("<f4", ())}[out_format]
+        n_out = bus.n_frames
+        need = n_out * self.channels * _lib.PCM_BYTES[ocode]
+        if out is None:
+            out = np.empty(max(need, 1), np.uint8)
+        elif not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.flags.writeable and out.nbytes >= need):
+            raise ValueError(f"out must be a C-contiguous writable array of at least {need} bytes")
+        dst = out.reshape(-1).view(np.uint8)
+        got, clipped, peak, gain = C.c_size_t(0), C.c_uint64(0), C.c_float(0), C.c_float(0)
+        cap = dst.size // (self.channels * _lib.PCM_BYTES[ocode])
+        self._check(self._L.rc_engine_bus_frames(self._h, bus._h, C.c_void_p(dst.ctypes.data), cap, ocode, C.c_float(tp), C.byref(got),
+                                                 C.byref(peak), C.byref(gain), C.byref(clipped)))
+        assert got.value == n_out
+        self.last_peak, self.last_gain, self.last_clipped = np.float32(peak.value), np.float32(gain.value), int(clipped.value)
+        self._read_limiter_stats()
+        stats = {"peak": self.last_peak, "gain": self.last_gain, "clipped": self.last_clipped}
+        return dst[:need].view(dtype).reshape((n_out, self.channels) + tail), stats
 
     last_lufs: Optional[float] = None       # stretch_frames_loud: the integrated loudness before the gain (np.float32, -inf: none) ...
     last_true_peak: Optional[float] = None  # ... and the true peak before the gain (np.float32); last_gain is the gain
@@ -1194,4 +1322,4 @@ def stretch(channels_in, window_len=16384, factor=1.0, amplitude=1.0, pitch_mult
 
 __all__ = ["AudioSpec", "AudioBus", "Engine", "ReFFT", "Stretcher", "StretcherProcessor", "stretch",
            "derive_params", "offline_output_len", "load_kernel_library", "RocoderError", "compile_device_kernel",
-           "DeviceKernelCompileError", "time_map_output_len", "time_map_curve", "warp_table", "warp_curve"]
+           "DeviceKernelCompileError", "time_map_output_len", "time_map_curve", "warp_table", "warp_curve", "Bus", "mix_envelope"]
