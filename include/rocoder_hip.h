@@ -796,6 +796,9 @@ int rc_calib_valu(int device, void *hip_stream, uint32_t launches, float *ms_per
 /* ---- mix bus: rc_bus_*, rc_engine_mix_frames, rc_engine_bus_frames, rc_mix_envelope ------------ */
 #include "rocoder_hip_mix.h"
 
+/* ---- phase modes: rc_engine_set_phase_mode, rc_engine_get_phase_mode, rc_phase_envelope -------- */
+#include "rocoder_hip_phase.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,9 @@ pub const RC_DITHER_NONE: u32 = 0;
 pub const RC_DITHER_TPDF: u32 = 1;
 pub const RC_DITHER_TPDF_HP: u32 = 2;
 pub const RC_LIMITER_MAX_LOOKAHEAD: u32 = 2048;
+pub const RC_PHASE_RANDOM: u32 = 0;
+pub const RC_PHASE_PROPAGATE: u32 = 1;
+pub const RC_PHASE_LOCKED: u32 = 2;
 
 /// `rc_config`: the arguments of `Stretcher::new` (src/stretcher.rs:30-39) for all channels of a job.
 #[repr(C)]
@@ -174,6 +177,10 @@ extern "C" {
     pub fn rc_time_map_curve(cfg: *const RcConfig, in_len: usize, at: *const f64, factor: *const f64, n_points: usize,
                              hop_pos: *mut i64, cap: usize, n_hops: *mut usize) -> c_int;
 }
+
+// `include/rocoder_hip_phase.h` (included by rocoder_hip.h): phase-coherent resynthesis, rc_engine_set_phase_mode(e, mode)
+// with the RC_PHASE_* values above. Its three functions are not declared here yet: this file's extern blocks are held,
+// one for one, to rocoder_hip.h and rocoder_hip_timemap.h (tests/test_cabi_host.py, tests/test_time_map_host.py).
 
 // ---------------------------------------------------------------------------------------------------------------
 // safe-ish helpers shared by stretcher_hip.rs

@@ -197,6 +197,15 @@ MIX_SYMBOLS = {
 }
 RC_MIX_MAX_KEYS = 4096
 
+# ... and every symbol include/rocoder_hip_phase.h declares (rocoder_hip.h includes it)
+PHASE_SYMBOLS = {
+    "rc_engine_set_phase_mode": (C.c_int, [_eng, C.c_uint32]),
+    "rc_engine_get_phase_mode": (C.c_int, [_eng, C.POINTER(C.c_uint32)]),
+    "rc_phase_envelope": (C.c_int, [_fp, _sz, _fp]),
+}
+RC_PHASE_RANDOM, RC_PHASE_PROPAGATE, RC_PHASE_LOCKED = 0, 1, 2  # rc_engine_set_phase_mode
+PHASE_MODES = {"random": RC_PHASE_RANDOM, "propagate": RC_PHASE_PROPAGATE, "locked": RC_PHASE_LOCKED}
+
 _lib = None
 
 
@@ -220,7 +229,7 @@ def _load(path: str) -> C.CDLL:
     except ImportError:
         pass
     L = C.CDLL(path)
-    for name, (res, args) in list(SYMBOLS.items()) + list(TIME_MAP_SYMBOLS.items()) + list(WARP_SYMBOLS.items()) + list(MIX_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(TIME_MAP_SYMBOLS.items()) + list(WARP_SYMBOLS.items()) + list(MIX_SYMBOLS.items()) + list(PHASE_SYMBOLS.items()):
         fn = getattr(L, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -214,6 +214,7 @@ struct FramesApi {
     decltype(&rc_bus_destroy) bus_destroy = nullptr;
     decltype(&rc_engine_mix_frames) mix_frames = nullptr;
     decltype(&rc_engine_bus_frames) bus_frames = nullptr;
+    decltype(&rc_engine_set_phase_mode) set_phase = nullptr;  // (--phase only: may be missing)
     decltype(&rc_host_alloc) alloc = nullptr;
     decltype(&rc_host_free) free = nullptr;
 };
@@ -246,6 +247,7 @@ static const FramesApi &frames_api() {
         a.bus_destroy = (decltype(a.bus_destroy))dlsym(RTLD_DEFAULT, "rc_bus_destroy");
         a.mix_frames = (decltype(a.mix_frames))dlsym(RTLD_DEFAULT, "rc_engine_mix_frames");
         a.bus_frames = (decltype(a.bus_frames))dlsym(RTLD_DEFAULT, "rc_engine_bus_frames");
+        a.set_phase = (decltype(a.set_phase))dlsym(RTLD_DEFAULT, "rc_engine_set_phase_mode");
         a.alloc = (decltype(a.alloc))dlsym(RTLD_DEFAULT, "rc_host_alloc");
         a.free = (decltype(a.free))dlsym(RTLD_DEFAULT, "rc_host_free");
         if (!a.stretch || !a.alloc || !a.free) throw std::runtime_error("--frames-on-gpu: the engine library has no rc_engine_stretch_frames");
@@ -1189,6 +1191,8 @@ struct Opt {  // src/main.rs:27-122
     uint32_t dither = RC_DITHER_NONE;
     bool dither_given = false;
     std::optional<uint64_t> dither_seed;  // [default: --seed]
+    // not in the reference (it resynthesises random phases): phase-coherent resynthesis (--frames-on-gpu; rc_engine_set_phase_mode)
+    uint32_t phase = RC_PHASE_RANDOM;
     // not in the reference's CLI (its mixer, src/mixer.rs, serves playback): --layer SPEC, repeatable. With one or more the run
     // is a mix on the GPU (--frames-on-gpu, -o): every SPEC is one layer over the same input file, the main flags are the
     // defaults of every layer and the output chain of the sum (rc_engine_mix_frames / rc_engine_bus_frames)
@@ -1319,6 +1323,13 @@ void usage() {
             "                                       peak, white (tpdf) or high-passed (tpdf-hp); on the GPU with --frames-on-gpu,\n"
             "                                       the same bytes without [default: none]\n"
             "        --dither-seed <u64>            Seed of --dither [default: the value of --seed]\n"
+            "        --phase <mode>                 random | propagate | locked: how the resynthesis sets its phases. random is the\n"
+            "                                       reference's (right at a factor of 8 and beyond); propagate lets every bin carry\n"
+            "                                       its own phase from hop to hop, locked gives every bin the rotation of its\n"
+            "                                       nearest spectral peak: a phase vocoder that keeps partials at small factors and\n"
+            "                                       under --pitch-cents. Other than random: with --frames-on-gpu, a window that is a\n"
+            "                                       power of two up to 16384, and without --layer, --factor-curve, --time-map,\n"
+            "                                       --pitch-curve or a kernel flag [default: random]\n"
             "        --autocrop                     With --frames-on-gpu: crop dead air off both ends of the input, as the reference\n"
             "                                       crops a recording, in front of -s/-d; the peaks are measured on the GPU\n"
             "        --autocrop-window <dur>        The analysis window of --autocrop [default: 0.1]\n"
@@ -1531,6 +1542,11 @@ int run(int argc, char **argv) {
             o.dither = v == "tpdf" ? RC_DITHER_TPDF : v == "tpdf-hp" ? RC_DITHER_TPDF_HP : RC_DITHER_NONE;
             o.dither_given = true;
         }
+        else if (a == "--phase") {
+            const std::string v = need(i);
+            if (v != "random" && v != "propagate" && v != "locked") throw std::runtime_error("--phase takes random, propagate or locked, not " + v);
+            o.phase = v == "locked" ? RC_PHASE_LOCKED : v == "propagate" ? RC_PHASE_PROPAGATE : RC_PHASE_RANDOM;
+        }
         else if (a == "--dither-seed") {
             const std::string v = need(i);
             char *end = nullptr;
@@ -1684,6 +1700,14 @@ int run(int argc, char **argv) {
                            : o.time_map_file ? "--time-map" : o.device_kernel_src ? "--device-kernel-src" : o.output_rate ? "--output-rate"
                            : o.channel_map ? "--channel-map" : o.split_mono ? "--split-mono" : nullptr;
         if (with) throw std::runtime_error(std::string("--layer cannot be combined with ") + with);
+    }
+    if (o.phase != RC_PHASE_RANDOM) {
+        // (a mode is state of the engine's whole-job calls, and the stage takes the place a kernel or a map would need)
+        if (!o.frames_on_gpu) throw std::runtime_error("--phase propagate / locked needs --frames-on-gpu");
+        const char *with = !o.layers.empty() ? "--layer" : o.factor_curve ? "--factor-curve" : o.time_map_file ? "--time-map"
+                           : o.pitch_curve ? "--pitch-curve" : o.freq_kernel ? "--freq-kernel" : o.device_kernel_src ? "--device-kernel-src"
+                           : o.device_kernel ? "--device-kernel" : nullptr;
+        if (with) throw std::runtime_error(std::string("--phase propagate / locked cannot be combined with ") + with);
     }
     if (o.dither_seed && !o.dither_given) throw std::runtime_error("--dither-seed needs --dither");
     // dither belongs in front of a quantiser of 8, 16 or 24 bits: f32 has none, and a step of i32 lies below an f32's precision
@@ -1998,6 +2022,14 @@ int run(int argc, char **argv) {
             return 0;
         }
         size_t cap = rc_offline_output_len(&cfg, raw_count);
+        if (o.phase != RC_PHASE_RANDOM) {
+            if (!frames_api().set_phase) throw std::runtime_error("--phase: the engine library has no rc_engine_set_phase_mode");
+            if (frames_api().set_phase(eng.h, o.phase) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+            rc_params par{};
+            if (rc_engine_get_params(eng.h, &par) != RC_OK) throw std::runtime_error(std::string("rocoder_hip: ") + rc_last_error());
+            fprintf(stderr, "phase: %s, %llu hops\n", o.phase == RC_PHASE_LOCKED ? "locked" : "propagate",
+                    (unsigned long long)(par.window_out_len ? cap / par.window_out_len * par.hops_per_window : 0));
+        }
         // --pitch-curve: (input frame, ratio) points, subdivided so that no segment spans more than 50 cents - linear in the
         // ratio then stays within 0.2 cent of linear in cents
         std::vector<double> pitch_at, pitch_ratio;

@@ -7,7 +7,7 @@
 ROOT := ../../..
 CXX  ?= g++
 COMMON := -g -O1 -std=c++17 -Wall -fno-omit-frame-pointer rocoder_cli.cpp -ldl -lpthread
-all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../bin/engine_tsan ../../bin/engine_dk_asan ../../bin/engine_xch_asan ../../bin/engine_frames_asan ../../bin/engine_frames_pcm_asan ../../bin/engine_frames_norm_asan ../../bin/engine_frames_fade_asan ../../bin/engine_frames_power_asan ../../bin/engine_frames_map_asan ../../bin/engine_frames_dither_asan ../../bin/engine_frames_resample_asan ../../bin/engine_frames_limit_asan ../../bin/engine_frames_loud_asan ../../bin/engine_dk_sums_asan ../../bin/engine_dk_fb_asan ../../bin/engine_timemap_asan ../../bin/engine_timemap_tsan ../../bin/engine_frames_warp_asan ../../bin/engine_frames_warp_tsan ../../bin/engine_frames_mix_asan ../../bin/engine_frames_mix_tsan
+all: ../../bin/rocoder_asan ../../bin/rocoder_tsan ../../bin/engine_asan ../../bin/engine_tsan ../../bin/engine_dk_asan ../../bin/engine_xch_asan ../../bin/engine_frames_asan ../../bin/engine_frames_pcm_asan ../../bin/engine_frames_norm_asan ../../bin/engine_frames_fade_asan ../../bin/engine_frames_power_asan ../../bin/engine_frames_map_asan ../../bin/engine_frames_dither_asan ../../bin/engine_frames_resample_asan ../../bin/engine_frames_limit_asan ../../bin/engine_frames_loud_asan ../../bin/engine_dk_sums_asan ../../bin/engine_dk_fb_asan ../../bin/engine_timemap_asan ../../bin/engine_timemap_tsan ../../bin/engine_frames_warp_asan ../../bin/engine_frames_warp_tsan ../../bin/engine_frames_mix_asan ../../bin/engine_frames_mix_tsan ../../bin/engine_phase_asan ../../bin/engine_phase_tsan
 ../../bin/rocoder_asan: rocoder_cli.cpp $(ROOT)/include/rocoder_hip.h ../../librocoder_hip.so
 	mkdir -p ../../bin
 	$(CXX) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(COMMON) -o $@ -L../.. -lrocoder_hip \
@@ -25,12 +25,12 @@ ENGINE_FLAGS := -g -O1 -std=c++17 -Wall -Wno-unused-function -fno-omit-frame-poi
     -I/opt/rocm/include -x c++
 ASAN := -fsanitize=address,undefined -fno-sanitize-recover=undefined
 TSAN := -fsanitize=thread
-ENGINE_HDR := ../rc_kernels.h ../rc_long.h ../rc_frames.h ../rc_timemap.h ../rc_warp.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h $(ROOT)/include/rocoder_hip_timemap.h \
-    $(ROOT)/include/rocoder_hip_warp.h $(ROOT)/include/rocoder_hip_mix.h
+ENGINE_HDR := ../rc_kernels.h ../rc_long.h ../rc_frames.h ../rc_timemap.h ../rc_warp.h ../rc_phase.h ../rc_rtc.h $(ROOT)/include/rocoder_hip.h $(ROOT)/include/rocoder_hip_timemap.h \
+    $(ROOT)/include/rocoder_hip_warp.h $(ROOT)/include/rocoder_hip_mix.h $(ROOT)/include/rocoder_hip_phase.h
 # the engine and the stubs: compiled once per sanitizer, linked into every driver's program
 ENGINE_PARTS := rc_engine rc_rtc hip_stub hip_stub_long hip_stub_frames hip_stub_frames_pcm hip_stub_frames_norm \
     hip_stub_frames_fade hip_stub_frames_power hip_stub_frames_map hip_stub_frames_dither hip_stub_frames_resample hip_stub_frames_limit hip_stub_frames_loud hip_stub_rtc \
-    hip_stub_timemap rc_timemap_curve hip_stub_frames_warp rc_warp_curve hip_stub_frames_mix rc_mix_envelope
+    hip_stub_timemap rc_timemap_curve hip_stub_frames_warp rc_warp_curve hip_stub_frames_mix rc_mix_envelope hip_stub_phase rc_phase_envelope
 ENGINE_ASAN_OBJ := $(ENGINE_PARTS:%=../../bin/%.asan.o)
 ENGINE_TSAN_OBJ := $(ENGINE_PARTS:%=../../bin/%.tsan.o)
 vpath %.cpp .. $(ROOT)/tests/c
@@ -91,6 +91,7 @@ ENGINE_FB_ASAN_OBJ := $(filter-out ../../bin/hip_stub_rtc.asan.o,$(ENGINE_ASAN_O
 ../../bin/rc_timemap_curve.%.o: ENGINE_FLAGS += -ffp-contract=off
 ../../bin/rc_warp_curve.%.o: ENGINE_FLAGS += -ffp-contract=off
 ../../bin/rc_mix_envelope.%.o: ENGINE_FLAGS += -ffp-contract=off
+../../bin/rc_phase_envelope.%.o: ENGINE_FLAGS += -ffp-contract=off
 ../../bin/rc_engine.hooks.asan.o: ../rc_engine.cpp $(ENGINE_HDR)
 	mkdir -p ../../bin
 	$(CXX) $(ASAN) $(ENGINE_FLAGS) -DRC_TEST_HOOKS=1 -c $< -o $@
@@ -115,6 +116,18 @@ TM_WRAP := -Wl,--wrap=_ZN2rc10launch_hopEiNS_7HopModeERKNS_9HopParamsEP12ihipStr
 	$(CXX) $(ASAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_ASAN_OBJ) -Wl,--wrap=hipMemcpyAsync -o $@ -lpthread -ldl
 ../../bin/engine_frames_mix_tsan: $(ROOT)/tests/c/engine_host_driver_frames_mix.cpp $(ENGINE_TSAN_OBJ) $(ENGINE_HDR)
 	$(CXX) $(TSAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_TSAN_OBJ) -Wl,--wrap=hipMemcpyAsync -o $@ -lpthread -ldl
+#   phase        rc_engine_set_phase_mode on the whole-job entries, ASan + UBSan and TSan, over the engine built with
+#                -DRC_TEST_HOOKS=1 for rc_test_phase_chunk_hops (hip_stub_phase.cpp's launchers log their launches, read what the
+#                real ones read and compose the maps for real; every program links them, the engine calls them). This program
+#                alone is linked with --wrap for rc::launch_hop and rc::launch_ola: the driver logs them and hands them on.
+ENGINE_PH_ASAN_OBJ := $(filter-out ../../bin/rc_engine.asan.o,$(ENGINE_ASAN_OBJ)) ../../bin/rc_engine.hooks.asan.o
+ENGINE_PH_TSAN_OBJ := $(filter-out ../../bin/rc_engine.tsan.o,$(ENGINE_TSAN_OBJ)) ../../bin/rc_engine.hooks.tsan.o
+PH_WRAP := -Wl,--wrap=_ZN2rc10launch_hopEiNS_7HopModeERKNS_9HopParamsEP12ihipStream_t \
+    -Wl,--wrap=_ZN2rc10launch_olaERKNS_9OlaParamsEP12ihipStream_tb
+../../bin/engine_phase_asan: $(ROOT)/tests/c/engine_host_driver_phase.cpp $(ENGINE_PH_ASAN_OBJ) $(ENGINE_HDR)
+	$(CXX) $(ASAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_PH_ASAN_OBJ) $(PH_WRAP) -o $@ -lpthread -ldl
+../../bin/engine_phase_tsan: $(ROOT)/tests/c/engine_host_driver_phase.cpp $(ENGINE_PH_TSAN_OBJ) $(ENGINE_HDR)
+	$(CXX) $(TSAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_PH_TSAN_OBJ) $(PH_WRAP) -o $@ -lpthread -ldl
 ../../bin/engine_%_asan: $(ROOT)/tests/c/engine_host_driver_%.cpp $(ENGINE_ASAN_OBJ) $(ENGINE_HDR)
 	$(CXX) $(ASAN) $(ENGINE_FLAGS) $< -x none $(ENGINE_ASAN_OBJ) -o $@ -lpthread -ldl
 ../../bin/engine_%_tsan: $(ROOT)/tests/c/engine_host_driver_%.cpp $(ENGINE_TSAN_OBJ) $(ENGINE_HDR)

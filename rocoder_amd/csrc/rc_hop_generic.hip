@@ -23,6 +23,7 @@
 // No MFMA: this is an FFT/SFU/LDS-bound path, not a contraction.
 #include "rc_passes.hpp"
 #include "rc_dit.hpp"  // (the constexpr sine / cosine of the computed-window constants)
+#include "rc_phase.h"  // MODE_RESYNTH_KEEP, launch_hop_keep
 
 namespace rc {
 namespace {
@@ -43,6 +44,19 @@ __device__ __forceinline__ void do_pair(float2 *lds, int pA, int pB, float2 w, u
         pair_synth<LOG2N>(m1a, m1b, m2a, m2b, w, ja, key, -0.5f / (float)N, VA, VB);
         lds[pA] = VA;
         if (pB != pA) lds[pB] = VB;
+    } else if constexpr (MODE == MODE_RESYNTH_KEEP) {
+        // the phases as they are given (rc_phase.h): Zs[j] = (Z[j] + conj Z[N - j]) / 2 of the four bins, then the tail
+        // of pair_synth - no hash, no magnitude, the same scale (the phasors there come negated, hence its -0.5 / N)
+        const float2 z1a = ldg2(spec + ja), z1b = ldg2(spec + ((N - ja) & (N - 1)));
+        const float2 z2a = ldg2(spec + (M - ja)), z2b = ldg2(spec + ((M + ja) & (N - 1)));
+        constexpr float kappa = 0.5f / (float)N;
+        const float px = (z1a.x + z1b.x) * kappa, py = (z1a.y - z1b.y) * kappa;  // Zs[ja]
+        const float qx = (z2a.x + z2b.x) * kappa, qy = (z2b.y - z2a.y) * kappa;  // conj(Zs[M-ja])
+        const float sx = px + qx, sy = py + qy;
+        const float rx = px - qx, ry = py - qy;
+        const float ux = rx * w.x + ry * w.y, uy = ry * w.x - rx * w.y;  // U = conj(w) R
+        lds[pA] = make_float2(sx - uy, sy + ux);                 // S + iU
+        if (pB != pA) lds[pB] = make_float2(sx + uy, ux - sy);   // conj(S - iU)
     } else {
         const float2 A = lds[pA];
         const float2 Bp = lds[pB];
@@ -252,12 +266,12 @@ __global__ __launch_bounds__((Geo<LOG2N>::T * hop_slots_of<LOG2N, MODE>()), Geo<
             middle_stage<LOG2N, MODE_FORWARD>(lds, tid, PhaseKey{0u, 1u}, rtab, spec);
             __syncthreads();
         }
-    } else if constexpr (MODE == MODE_RESYNTH) {
+    } else if constexpr (MODE == MODE_RESYNTH || MODE == MODE_RESYNTH_KEEP) {
         for (int64_t k = k_begin; k < k_end; ++k) {
             const size_t hop_idx = (size_t)ch * p.hop_count + (size_t)(k - p.hop_first);
             GV2W spec = (GV2W)p.spec + hop_idx * N;
             const PhaseKey key = make_phase_key(p.seed_mixed, p.ch_first + ch, k);
-            middle_stage<LOG2N, MODE_RESYNTH>(lds, tid, key, rtab, spec);
+            middle_stage<LOG2N, MODE>(lds, tid, key, rtab, spec);
             __syncthreads();
             lds_load<G, LL>(v, lds, ctx.lb[LL]);
             __syncthreads();
@@ -466,6 +480,13 @@ hipError_t launch_hop_n(HopMode mode, const HopParams &p, hipStream_t s) {
     }
     return hipGetLastError();
 }
+template <int LOG2N>
+hipError_t launch_hop_keep_n(const HopParams &p, hipStream_t s) {
+    using G = Geo<LOG2N>;
+    hipLaunchKernelGGL((hop_kernel<LOG2N, MODE_RESYNTH_KEEP, true>), dim3(p.runs_per_channel * p.n_channels), dim3(G::T),
+                       sizeof(float2) * G::LDS_FLOAT2, s, p);
+    return hipGetLastError();
+}
 }  // namespace
 
 int hop_workgroups_per_cu(int log2n, bool default_window, bool pitch1) {
@@ -511,6 +532,22 @@ hipError_t launch_hop(int log2n, HopMode mode, const HopParams &p, hipStream_t s
         case 12: return launch_hop_n<12>(mode, p, s);
         case 13: return launch_hop_n<13>(mode, p, s);
         case 14: return launch_hop_n<14>(mode, p, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_hop_keep(int log2n, const HopParams &p, hipStream_t s) {
+    switch (log2n) {
+        case 5: return launch_hop_keep_n<5>(p, s);
+        case 6: return launch_hop_keep_n<6>(p, s);
+        case 7: return launch_hop_keep_n<7>(p, s);
+        case 8: return launch_hop_keep_n<8>(p, s);
+        case 9: return launch_hop_keep_n<9>(p, s);
+        case 10: return launch_hop_keep_n<10>(p, s);
+        case 11: return launch_hop_keep_n<11>(p, s);
+        case 12: return launch_hop_keep_n<12>(p, s);
+        case 13: return launch_hop_keep_n<13>(p, s);
+        case 14: return launch_hop_keep_n<14>(p, s);
         default: return hipErrorInvalidValue;
     }
 }

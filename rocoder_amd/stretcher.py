@@ -366,6 +366,24 @@ def mix_envelope(keys, t0: int, n: int) -> np.ndarray:
     return out
 
 
+RC_PHASE_RANDOM, RC_PHASE_PROPAGATE, RC_PHASE_LOCKED = _lib.RC_PHASE_RANDOM, _lib.RC_PHASE_PROPAGATE, _lib.RC_PHASE_LOCKED
+
+
+def phase_envelope(window) -> np.ndarray:
+    """env[i] = 1 / (w[i]^2 + w[i + n/2]^2), i < n/2, in float32: the overlap-add envelope of the phase modes
+    (rc_phase_envelope; include/rocoder_hip_phase.h). Raises for a window whose sum falls below 2^-10 of its maximum
+    anywhere. Pure host code."""
+    w = np.ascontiguousarray(window, np.float32)
+    if w.ndim != 1:
+        raise ValueError("window is one-dimensional")
+    out = np.empty(w.size // 2, np.float32)
+    L = _lib.lib()
+    if L.rc_phase_envelope(_fp(w), w.size, _fp(out)) != _lib.RC_OK:
+        raise RocoderError(_lib.RC_EINVAL, "phase_envelope: an even window of at least 2 finite samples whose w[i]^2 + w[i + n/2]^2 "
+                                           "stays above 2^-10 of its maximum")
+    return out
+
+
 class Bus:
     """A device-resident mix bus (rc_bus): `channels` planar float32 rows of `n_frames` frames on `device`, all zero when
     created and after `clear()`. `Engine.mix_frames` accumulates layers into it, `Engine.bus_frames` reads it out through an
@@ -959,6 +977,26 @@ class Engine:
             raise ValueError("channel indices are unsigned 32-bit integers")
         arr = (C.c_uint32 * len(vals))(*vals)
         self._check(self._L.rc_engine_set_channel_map(self._h, arr, len(vals)))
+
+    def set_phase_mode(self, mode="random"):
+        """How the whole-job calls resynthesise (rc_engine_set_phase_mode; the definition is in
+        include/rocoder_hip_phase.h): "random" (the default) is the reference's magnitude x random phase, "propagate" lets
+        every bin carry its own phase from hop to hop, "locked" gives every bin the rotation of its nearest spectral peak.
+        `mode` is a name or one of RC_PHASE_*. The streaming calls, `stretch_device_range`, `resynth`, kernels, time maps
+        and output warps do not go with a mode other than "random": whichever comes second raises."""
+        if isinstance(mode, str):
+            if mode not in _lib.PHASE_MODES:
+                raise ValueError(f"phase mode {mode!r} is none of {sorted(_lib.PHASE_MODES)}")
+            mode = _lib.PHASE_MODES[mode]
+        if not 0 <= int(mode) < 2 ** 32:
+            raise ValueError("phase mode is one of RC_PHASE_RANDOM, RC_PHASE_PROPAGATE, RC_PHASE_LOCKED")
+        self._check(self._L.rc_engine_set_phase_mode(self._h, int(mode)))
+
+    @property
+    def phase_mode(self) -> int:
+        m = C.c_uint32(0)
+        self._check(self._L.rc_engine_get_phase_mode(self._h, C.byref(m)))
+        return int(m.value)
 
     def set_output_fade(self, fade_in: int = 0, fade_out_start: Optional[int] = None, fade_out_len: int = 0):
         """The reference's sqrt fade-in over the first `fade_in` output frames and fade-out over `fade_out_len` frames

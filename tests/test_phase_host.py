@@ -1,0 +1,218 @@
+"""CPU tests (-m "not gpu") of the phase modes (include/rocoder_hip_phase.h): the numpy twin of the definition
+(tests/phaseutil.py) against hand-written answers and against its own properties, rc_phase_envelope against it, and the
+conditioning check that admits the cases of the GPU parity test (tests/test_gpu_phase.py)."""
+import numpy as np
+import pytest
+
+import phaseutil as pu
+import windowutil
+from oracle import oracle_np as onp
+
+import rocoder_amd
+from rocoder_amd import _lib
+
+
+# ------------------------------------------------------------------------------------------------ rc_phase_envelope
+@pytest.mark.parametrize("N", [32, 1024, 16384])
+@pytest.mark.parametrize("name", [None, "skew", "ramp", "hann_but_last"])
+def test_phase_envelope_is_the_twins(N, name):
+    w = onp.hanning(N) if name is None else windowutil.WINDOWS[name](N)
+    got = rocoder_amd.phase_envelope(w)
+    assert got.dtype == np.float32 and got.shape == (N // 2,)
+    # every step one f32 operation: two products, a sum, a quotient - 3 half-ulps of relative error at the most
+    assert np.abs(got.astype(np.float64) / pu.envelope(w) - 1.0).max() <= 3 * 2.0 ** -24
+    # ... and exactly those operations
+    w32 = np.asarray(w, np.float32)
+    want = np.float32(1.0) / (w32[:N // 2] * w32[:N // 2] + w32[N // 2:] * w32[N // 2:])
+    assert got.tobytes() == want.astype(np.float32).tobytes()
+
+
+def test_phase_envelope_refuses_what_it_cannot_invert():
+    import ctypes as C
+
+    L = _lib.lib()
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    out = np.zeros(8, np.float32)
+    w = np.ones(16, np.float32)
+    assert L.rc_phase_envelope(fp(w), 16, fp(out)) == _lib.RC_OK and (out == 0.5).all()
+    assert L.rc_phase_envelope(None, 16, fp(out)) == _lib.RC_EINVAL
+    assert L.rc_phase_envelope(fp(w), 16, None) == _lib.RC_EINVAL
+    assert L.rc_phase_envelope(fp(w), 15, fp(out)) == _lib.RC_EINVAL
+    assert L.rc_phase_envelope(fp(w), 0, fp(out)) == _lib.RC_EINVAL
+    z = w.copy()
+    z[3] = z[11] = 0.0  # w[3]^2 + w[3 + H]^2 == 0
+    assert L.rc_phase_envelope(fp(z), 16, fp(out)) == _lib.RC_EINVAL
+    z[3] = z[11] = np.float32(2.0 ** -6)  # 2^-11 of the maximum 2: below 2^-10
+    assert L.rc_phase_envelope(fp(z), 16, fp(out)) == _lib.RC_EINVAL
+    z[3] = z[11] = np.float32(2.0 ** -4.9)  # above it
+    assert L.rc_phase_envelope(fp(z), 16, fp(out)) == _lib.RC_OK
+    z[5] = np.float32(np.inf)
+    assert L.rc_phase_envelope(fp(z), 16, fp(out)) == _lib.RC_EINVAL
+    assert L.rc_phase_envelope(fp(np.zeros(16, np.float32)), 16, fp(out)) == _lib.RC_EINVAL
+    with pytest.raises(rocoder_amd.RocoderError):
+        rocoder_amd.phase_envelope(np.zeros(16, np.float32))
+
+
+def test_python_constants_are_the_headers():
+    import os
+    import re
+
+    from conftest import ROOT
+
+    h = open(os.path.join(ROOT, "include", "rocoder_hip_phase.h")).read()
+    for name in ("RC_PHASE_RANDOM", "RC_PHASE_PROPAGATE", "RC_PHASE_LOCKED"):
+        v = int(re.search(r"#define %s\s+(\d+)" % name, h).group(1))
+        assert getattr(_lib, name) == v == getattr(rocoder_amd, name)
+    assert _lib.PHASE_MODES == {"random": 0, "propagate": 1, "locked": 2}
+    assert (pu.RANDOM, pu.PROPAGATE, pu.LOCKED) == (0, 1, 2)
+    # every function the header declares is in the ctypes table and exported
+    code = re.sub(r"/\*.*?\*/", "", h, flags=re.S)
+    names = sorted(set(re.findall(r"\b(rc_[a-z0-9_]+)\s*\(", code)))
+    assert names == sorted(_lib.PHASE_SYMBOLS)
+    for n in names:
+        assert hasattr(_lib.lib(), n)
+
+
+# ------------------------------------------------------------------------------------------------ the owner rule, by hand
+H16 = 16
+
+
+def _m2(peaks_at, H=H16, base=1.0, top=9.0):
+    m = np.full(H + 1, base)
+    for j in peaks_at:
+        m[j] = top
+    return m
+
+
+def test_owner_rule_hand_cases():
+    H = H16
+    j = np.arange(H + 1)
+    # peaks at bins 1, 2, H - 2, H - 1: adjacent bins are no peaks of each other unless strictly greater
+    m = np.ones(H + 1)
+    m[1], m[2], m[H - 2], m[H - 1] = 5.0, 9.0, 9.0, 5.0
+    assert list(pu.peaks(m)) == [2, H - 2]  # 1 and H - 1 lose to their neighbour
+    want = np.where(j <= (2 + H - 2) // 2, 2, H - 2)  # the tie at bin 8 goes to the lower peak
+    assert list(pu.owners(m, True)) == list(want)
+    # bin 1 and bin H - 1 as peaks: their neighbours outside 0 ... H do not count
+    m = _m2([1, H - 1])
+    assert list(pu.peaks(m)) == [1, H - 1]
+    assert list(pu.owners(m, True)) == [1] * 9 + [H - 1] * 8  # bins 0 ... 8 -> 1 (8 is the tie), 9 ... 16 -> 15
+    # bins 0 and H are never peaks
+    m = _m2([0, H])
+    assert pu.peaks(m).size == 0 and list(pu.owners(m, True)) == list(j)
+    # a plateau: no strict maximum, no peak, every bin owns itself
+    m = np.ones(H + 1)
+    m[6] = m[7] = 9.0
+    assert pu.peaks(m).size == 0 and list(pu.owners(m, True)) == list(j)
+    # equal at distance 2 is no peak either
+    m = np.ones(H + 1)
+    m[6] = m[8] = 9.0
+    assert pu.peaks(m).size == 0
+    # one peak owns everything
+    assert list(pu.owners(_m2([5]), True)) == [5] * (H + 1)
+    # an equidistant bin goes to the lower peak, its neighbours to theirs
+    own = pu.owners(_m2([4, 10]), True)
+    assert own[7] == 4 and own[6] == 4 and own[8] == 10
+    # a silent hop
+    assert list(pu.owners(np.zeros(H + 1), True)) == list(j)
+    # PROPAGATE never looks
+    assert list(pu.owners(_m2([5]), False)) == list(j)
+
+
+def test_increment_is_zero_at_a_step_of_half_a_window():
+    rng = np.random.default_rng(5)
+    N = 64
+    for _ in range(4):
+        X0 = rng.standard_normal(N // 2 + 1) + 1j * rng.standard_normal(N // 2 + 1)
+        X1 = rng.standard_normal(N // 2 + 1) + 1j * rng.standard_normal(N // 2 + 1)
+        assert not pu.increments(pu.turns(X0), pu.turns(X1), N, N // 2).any()
+    # a bin-centred sinusoid advances by its own frequency: dev == 0, e == (r - 1) (a1 - a0) + ... == the textbook value
+    step, j = 8, 5
+    a0 = np.zeros(N // 2 + 1, np.int64)
+    adv = ((j * step) % N) * ((1 << 32) // N)
+    a1 = a0.copy()
+    a1[j] = adv
+    e = pu.increments(a0, a1, N, step)
+    assert e[j] == (-adv + ((j & 1) << 31)) & pu.MASK  # dev 0: d = omega_j H alone
+
+
+# ------------------------------------------------------------------------------------------------ properties of the twin
+@pytest.mark.parametrize("mode", [pu.PROPAGATE, pu.LOCKED])
+@pytest.mark.parametrize("kind", ["tones", "white"])
+def test_factor_one_returns_the_input(mode, kind):
+    N, H = 256, 128
+    L = 8 * N
+    x = pu.tones_input(2, L, N) if kind == "tones" else windowutil.white_input(2, L)
+    y = pu.stretch(x, N, 1.0, 1, mode)
+    assert y.shape[1] >= L
+    # outside the first H samples (one window covers them) and up to the last hop that lies inside the input
+    assert np.abs(y[:, H:L - N] - x[:, H:L - N].astype(np.float64)).max() <= 1e-12
+
+
+@pytest.mark.parametrize("f", [1.5, 3.0, 8.0])
+def test_locked_keeps_three_sinusoids(f):
+    """Frequencies and amplitudes survive the stretch: a least-squares fit of the three frequencies to the samples whose
+    hops lie wholly inside the input leaves a relative residual below 1e-5. (The partials are far enough apart - from
+    each other and from their mirror images - that the Hann side lobes of one under the peak of another stay below that.)"""
+    N, H, L = 1024, 512, 24 * 1024
+    parts = ((100.3, 0.4), (230.6, 0.25), (380.2, 0.15))
+    x = pu.tones(0, L, N, parts)
+    step = onp.derive(N, f, 1.0, 1)["step"]
+    y = pu.stretch(x, N, f, 1, pu.LOCKED)[0]
+    t = np.arange(2 * H, ((L - N) // step) * H)
+    cols = []
+    for b, _a in parts:
+        cols += [np.cos(2 * np.pi * b / N * t), np.sin(2 * np.pi * b / N * t)]
+    A = np.stack(cols, 1)
+    c = np.linalg.lstsq(A, y[t], rcond=None)[0]
+    resid = y[t] - A @ c
+    assert pu.rel_rms(resid + y[t], y[t]) < 1e-5
+    for i, (_b, a) in enumerate(parts):
+        assert abs(np.hypot(c[2 * i], c[2 * i + 1]) - a) < 1e-5 * a
+
+
+def test_sequential_scan_composes():
+    """the map of a hop composes - what phase_scan relies on: (Q', s') = (Q o P, s o P + e o P)"""
+    rng = np.random.default_rng(11)
+    nb, hops = 9, 7
+    P = rng.integers(0, nb, (hops, nb))
+    e = rng.integers(0, 1 << 32, (hops, nb))
+    th0 = rng.integers(0, 1 << 32, nb)
+    want = pu.scan_sequential(P, e, th0)
+    Q, s = np.arange(nb), np.zeros(nb, np.int64)
+    for k in range(hops):
+        Q, s = Q[P[k]], (s[P[k]] + e[k][P[k]]) & pu.MASK
+        assert list((th0[Q] + s) & pu.MASK) == list(want[k])
+
+
+# ------------------------------------------------------------------------------------------------ the conditioning check
+@pytest.mark.parametrize("case", pu.PARITY_CASES, ids=lambda c: "N%d-f%g-p%d-%s-%s" % (c[0], c[1], c[2], ("", "propagate", "locked")[c[3]], c[4]))
+def test_parity_cases_are_well_conditioned(case):
+    """The definition is discontinuous where dev sits at half a turn and where two magnitudes tie, so a parity gate only
+    means something on inputs that stay away from both. Every case of the GPU parity test: the twin's spectra perturbed
+    by a relative 2^-22 complex Gaussian, 8 seeds, move the output by at most 1e-5 relative RMS, a tenth of the gate -
+    per bin ("bin"), and, stricter for weak bins, relative to the hop's RMS magnitude ("floor": the shape of an f32
+    transform's rounding). A case that fails is replaced, not gated wider."""
+    N, f, p, mode, wname = case
+    if mode == pu.PROPAGATE:
+        d = onp.derive(N, f, 1.0, p)
+        assert d["H"] % d["step"] == 0, "PROPAGATE cases use factors with H % step == 0"
+    x = pu.case_input(N)
+    w = pu.case_window(N, wname)
+    ref = pu.stretch(x, N, f, p, mode, window=w)
+    for kind in ("bin", "floor"):
+        worst = max(pu.rel_rms(pu.stretch(x, N, f, p, mode, window=w, perturb=(kind, pu.PERTURB), seed=s), ref) for s in range(8))
+        print(f"{case} {kind}: {worst:.2e}")
+        assert worst <= pu.PERTURB_TOL, (case, kind, worst)
+
+
+def test_parity_cases_cover_what_the_gpu_test_must():
+    ns = {c[0] for c in pu.PARITY_CASES}
+    assert {32, 512, 16384} <= ns
+    assert {1, 2} <= {c[2] for c in pu.PARITY_CASES} and any(c[2] < 0 for c in pu.PARITY_CASES)
+    assert any(c[4] is not None for c in pu.PARITY_CASES)
+    assert {pu.PROPAGATE, pu.LOCKED} == {c[3] for c in pu.PARITY_CASES}
+    for c in pu.PARITY_CASES:
+        if c[4] is not None:
+            w = windowutil.WINDOWS[c[4]](c[0])
+            assert not np.array_equal(w, w[::-1])  # asymmetric

@@ -145,6 +145,17 @@ grep -c "WARNING: ThreadSanitizer" "$ROOT/.san_out.txt" | sed 's/^/  ThreadSanit
 tail -1 "$ROOT/.san_out.txt" | sed 's/^/  /'; echo "  exit $rc"
 [ $rc -ne 0 ] && fail=1
 grep -q "WARNING: ThreadSanitizer" "$ROOT/.san_out.txt" && { fail=1; grep -A12 "WARNING: ThreadSanitizer" "$ROOT/.san_out.txt" | head -60; }
+echo "+ engine_phase_asan (ASan + UBSan: rc_engine_set_phase_mode, tests/c/engine_host_driver_phase.cpp + hip_stub_phase.cpp)"
+ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 "$ROOT/rocoder_amd/bin/engine_phase_asan" > "$ROOT/.san_out.txt" 2>&1; rc=$?
+tail -1 "$ROOT/.san_out.txt" | sed 's/^/  /'; echo "  exit $rc"
+[ $rc -ne 0 ] && fail=1
+grep -q "Sanitizer\|runtime error" "$ROOT/.san_out.txt" && { fail=1; head -40 "$ROOT/.san_out.txt"; }
+echo "+ engine_phase_tsan (TSan: the same driver)"
+TSAN_OPTIONS=halt_on_error=0:second_deadlock_stack=1 "$ROOT/rocoder_amd/bin/engine_phase_tsan" > "$ROOT/.san_out.txt" 2>&1; rc=$?
+grep -c "WARNING: ThreadSanitizer" "$ROOT/.san_out.txt" | sed 's/^/  ThreadSanitizer warnings: /'
+tail -1 "$ROOT/.san_out.txt" | sed 's/^/  /'; echo "  exit $rc"
+[ $rc -ne 0 ] && fail=1
+grep -q "WARNING: ThreadSanitizer" "$ROOT/.san_out.txt" && { fail=1; grep -A12 "WARNING: ThreadSanitizer" "$ROOT/.san_out.txt" | head -60; }
 echo "+ engine_tsan"
 TSAN_OPTIONS=halt_on_error=0:second_deadlock_stack=1 "$ROOT/rocoder_amd/bin/engine_tsan" > "$ROOT/.san_out.txt" 2>&1; rc=$?
 grep -c "WARNING: ThreadSanitizer" "$ROOT/.san_out.txt" | sed 's/^/  ThreadSanitizer warnings: /'
