@@ -9,7 +9,9 @@
 //      phase-keeping synthesis, the overlap-add,
 //   2. theta zeroed at hop 0 and carried from chunk to chunk, in both modes and call after call,
 //   3. the overlap-add envelope and amplitude: the coherent table under a mode, the reference's bits again behind RANDOM,
-//   4. every refusal, in both orders of the two calls, with the mode left as it was.
+//   4. every refusal, in both orders of the two calls, with the mode left as it was,
+//   5. rc_test_phase_tap: the rows and the chunk table of the three-chunk job in arrays of exactly their size, the same
+//      launches and the same output with the tap set, a job refused whole when any array is one element short.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -32,6 +34,8 @@ extern RcStubPhaseLaunch rc_stub_phase_log[1024];
 extern uint32_t rc_stub_phase_launches;
 void rc_stub_phase_note(const RcStubPhaseLaunch &l);
 extern "C" int rc_test_phase_chunk_hops(rc_engine *e, uint64_t n);  // (the engine of this program is the test-hook build)
+extern "C" int rc_test_phase_tap(rc_engine *e, float *spec, size_t spec_cap, uint32_t *qs, size_t qs_cap, uint32_t *base, size_t base_cap,
+                                 float *z, size_t z_cap, float *y, size_t y_cap, int64_t *chunks, size_t chunk_cap, uint64_t *n_chunks);
 
 // the stub's own functions under the names --wrap gives them, and what the engine's calls resolve to
 hipError_t real_launch_hop(int, rc::HopMode, const rc::HopParams &, hipStream_t) __asm__("__real__ZN2rc10launch_hopEiNS_7HopModeERKNS_9HopParamsEP12ihipStream_t");
@@ -48,7 +52,13 @@ hipError_t wrap_launch_hop(int log2n, rc::HopMode mode, const rc::HopParams &p, 
     g_env = p.env;
     g_amp = p.amp;
     g_last_mode = (int)mode;
-    if (mode == rc::MODE_FORWARD) rc_stub_phase_note(RcStubPhaseLaunch{10, p.hop_first, p.hop_count, 0, p.n_channels, 0, p.step, 0, 0, 0});
+    if (mode == rc::MODE_FORWARD) {
+        rc_stub_phase_note(RcStubPhaseLaunch{10, p.hop_first, p.hop_count, 0, p.n_channels, 0, p.step, 0, 0, 0});
+        // the stub's kernels compute nothing: mark every analysis row with (hop, channel) in bin 0 for the tap's check
+        for (uint32_t c = 0; p.spec && c < p.n_channels; ++c)
+            for (int64_t r = 0; r < p.hop_count; ++r)
+                p.spec[((size_t)c * p.hop_count + r) << log2n] = make_float2((float)(p.hop_first + r), (float)c);
+    }
     return real_launch_hop(log2n, mode, p, s);
 }
 hipError_t wrap_launch_ola(const rc::OlaParams &p, hipStream_t s, bool tail_only) {
@@ -178,6 +188,71 @@ int main() {
     rc_stub_phase_launches = 0;
     CHECK(rc_engine_stretch_device(e, d_in, L, L, d_out, n_out, n_out, &got, nullptr) == RC_OK);
     CHECK(rc_stub_phase_launches == 7 && rc_stub_phase_log[3].kind == 2 && rc_stub_phase_log[3].theta_in == 0 && rc_stub_phase_log[3].theta_out == 21);
+
+    // 5. the tap: arrays of exactly the job's size (one element more anywhere is an AddressSanitizer finding), chunks of 8
+    // hops again. The stub's rows by hand: apply leaves theta - the hop's index - in the real part of every bin, the
+    // synthesis in every sample; scan leaves Q = the identity and s = the hops since the chunk began; base is the carried
+    // state 0, 7, 15.
+    {
+        const size_t nb = H + 1, hops = 22;
+        const size_t n_spec = CH * (8 + 9 + 7) * N * 2, n_qs = CH * hops * 2 * nb, n_base = CH * 3 * nb, n_z = CH * hops * N * 2, n_y = CH * hops * N;
+        std::vector<float> spec(n_spec, -1.0f), z(n_z, -1.0f), y(n_y, -1.0f), plain(CH * n_out), tapped(CH * n_out);
+        std::vector<uint32_t> qs(n_qs, 0xA5A5A5A5u), base(n_base, 0xA5A5A5A5u);
+        std::vector<int64_t> table(3 * 11, -1);
+        uint64_t n_chunks = 99;
+        CHECK(rc_test_phase_chunk_hops(e, 8) == RC_OK);
+        CHECK(rc_engine_stretch_device(e, d_in, L, L, d_out, n_out, n_out, &got, nullptr) == RC_OK && rc_engine_synchronize(e) == RC_OK);
+        memcpy(plain.data(), d_out, plain.size() * sizeof(float));
+        CHECK(rc_test_phase_tap(nullptr, spec.data(), n_spec, qs.data(), n_qs, base.data(), n_base, z.data(), n_z, y.data(), n_y, table.data(), 3, &n_chunks) == RC_EINVAL);
+        CHECK(rc_test_phase_tap(e, spec.data(), n_spec, nullptr, n_qs, base.data(), n_base, z.data(), n_z, y.data(), n_y, table.data(), 3, &n_chunks) == RC_EINVAL);
+        CHECK(rc_test_phase_tap(e, spec.data(), n_spec, qs.data(), n_qs, base.data(), n_base, z.data(), n_z, y.data(), n_y, table.data(), 3, &n_chunks) == RC_OK);
+        CHECK(n_chunks == 0);
+        rc_stub_phase_launches = 0;
+        CHECK(rc_engine_stretch_device(e, d_in, L, L, d_out, n_out, n_out, &got, nullptr) == RC_OK && rc_engine_synchronize(e) == RC_OK);
+        CHECK(rc_stub_phase_launches == 3 * 7 && n_chunks == 3);  // (no launch more than without it)
+        memcpy(tapped.data(), d_out, tapped.size() * sizeof(float));
+        CHECK(memcmp(plain.data(), tapped.data(), plain.size() * sizeof(float)) == 0);
+        const int64_t want[3][11] = {{0, 8, 16, 0, CH, 0, 0, 0, 0, 0, 0},
+                                     {8, 8, 16, 0, CH, 1, (int64_t)(CH * 8 * N * 2), (int64_t)(CH * 8 * 2 * nb), (int64_t)(CH * nb), (int64_t)(CH * 8 * N * 2), (int64_t)(CH * 8 * N)},
+                                     {16, 6, 16, 0, CH, 1, (int64_t)(CH * 17 * N * 2), (int64_t)(CH * 16 * 2 * nb), (int64_t)(2 * CH * nb), (int64_t)(CH * 16 * N * 2), (int64_t)(CH * 16 * N)}};
+        CHECK(memcmp(table.data(), want, sizeof want) == 0);
+        for (int c = 0; c < 3; ++c) {
+            const int64_t k0 = want[c][0], kc = want[c][1], halo = want[c][5];
+            for (uint32_t ch = 0; ch < CH; ++ch) {
+                for (size_t j = 0; j < nb; ++j) CHECK(base[(size_t)want[c][8] + ch * nb + j] == (c == 0 ? 0u : c == 1 ? 7u : 15u));
+                for (int64_t r = 0; r < kc; ++r) {
+                    const uint32_t hop = (uint32_t)(k0 + r), since = (uint32_t)(k0 == 0 ? r : r + 1);  // (hop 0 adds nothing)
+                    const uint32_t *row = qs.data() + want[c][7] + ((size_t)ch * kc + r) * 2 * nb;
+                    for (size_t j = 0; j < nb; ++j) CHECK(row[j] == j && row[nb + j] == since);
+                    const float *zr = z.data() + want[c][9] + ((size_t)ch * kc + r) * N * 2, *yr = y.data() + want[c][10] + ((size_t)ch * kc + r) * N;
+                    for (size_t j = 0; j < nb; ++j) CHECK(zr[2 * j] == (float)hop && zr[2 * j + 1] == 0.0f);
+                    for (size_t i = 0; i < N; ++i) CHECK(yr[i] == (float)hop);
+                }
+                // the analysis rows, the halo hop in front: bin 0 holds (hop, channel) (wrap_launch_hop), the rest zeros
+                for (int64_t r = 0; r < kc + halo; ++r) {
+                    const float *xr = spec.data() + want[c][6] + ((size_t)ch * (kc + halo) + r) * N * 2;
+                    CHECK(xr[0] == (float)(k0 - halo + r) && xr[1] == (float)ch);
+                    for (size_t i = 2; i < 2 * N; ++i) CHECK(xr[i] == 0.0f);
+                }
+            }
+        }
+        // one element short, in every array in turn: refused before any of the job's hops runs, nothing cut short
+        const size_t caps[6] = {n_spec, n_qs, n_base, n_z, n_y, 3};
+        for (int short_one = 0; short_one < 6; ++short_one) {
+            size_t c6[6];
+            for (int i = 0; i < 6; ++i) c6[i] = caps[i] - (i == short_one ? 1 : 0);
+            CHECK(rc_test_phase_tap(e, spec.data(), c6[0], qs.data(), c6[1], base.data(), c6[2], z.data(), c6[3], y.data(), c6[4], table.data(), c6[5], &n_chunks) == RC_OK);
+            rc_stub_phase_launches = 0;
+            CHECK(rc_engine_stretch_device(e, d_in, L, L, d_out, n_out, n_out, &got, nullptr) == RC_EINVAL && names("rc_test_phase_tap"));
+            CHECK(rc_stub_phase_launches == 0 && n_chunks == 0);
+        }
+        // the tap removed: the job runs as before and the arrays stay as they are
+        CHECK(rc_test_phase_tap(e, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr) == RC_OK);
+        n_chunks = 42;
+        CHECK(rc_engine_stretch_device(e, d_in, L, L, d_out, n_out, n_out, &got, nullptr) == RC_OK && rc_engine_synchronize(e) == RC_OK);
+        CHECK(n_chunks == 42 && memcmp(plain.data(), d_out, plain.size() * sizeof(float)) == 0);
+        CHECK(rc_test_phase_chunk_hops(e, 0) == RC_OK);
+    }
 
     // 4a. the mode first: the seam, the range entry and the single hop are unsupported and say which mode is set
     {

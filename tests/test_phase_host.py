@@ -1,6 +1,7 @@
 """CPU tests (-m "not gpu") of the phase modes (include/rocoder_hip_phase.h): the numpy twin of the definition
 (tests/phaseutil.py) against hand-written answers and against its own properties, rc_phase_envelope against it, and the
-conditioning check that admits the cases of the GPU parity test (tests/test_gpu_phase.py)."""
+conditioning check that admits the cases of the GPU parity test (tests/test_gpu_phase.py), and the stage verifiers of the
+replay test (tests/test_gpu_phase_replay.py) held to the definition's own rows and to the mutants each must catch."""
 import numpy as np
 import pytest
 
@@ -207,6 +208,29 @@ def test_parity_cases_are_well_conditioned(case):
 
 
 def test_parity_cases_cover_what_the_gpu_test_must():
+    # the replay cases (tests/test_gpu_phase_replay.py): every instantiation of hop_kernel<LOG2N, MODE_RESYNTH_KEEP> under
+    # both modes, every factor and pitch the issue names, the channel counts, the caller's windows, the edge lengths - and
+    # PARITY_CASES once more, so that the two methods meet
+    R = pu.REPLAY_CASES
+    for mode in (pu.PROPAGATE, pu.LOCKED):
+        assert {1 << n for n in range(5, 15)} <= {c.N for c in R if c.mode == mode}
+        assert {0.75, 1.5, 2.0, 3.0, 5.0, 8.0} <= {c.f for c in R if c.mode == mode}
+        assert {c.N for c in R if c.mode == mode and c.group == "edge"} == {256, 1024}
+        assert {c.window for c in R if c.mode == mode and c.N in (256, 4096)} >= {"skew", "ramp"}
+        assert {"bursts", "dc", "white_full", "white_1e-6"} <= {c.signal for c in R if c.mode == mode}
+    assert {1, 2, 3, -2, -3} <= {c.p for c in R}
+    assert {1, 2, 3, 5} <= {c.ch for c in R if c.N == 64} and {1, 2, 3, 5} <= {c.ch for c in R if c.N == 256}
+    assert any(c.N == 4096 and c.ch == 3 for c in R)
+    assert {c.mode for c in R if c.signal in ("click", "comb")} == {pu.PROPAGATE}  # (they tie: test_clicks_tie_...)
+    for N in (256, 1024):
+        step = onp.derive(N, [c.f for c in R if c.group == "edge" and c.N == N][0], 1.0, 1)["step"]
+        assert {c.L for c in R if c.group == "edge" and c.N == N} == {0, 1, N - 1, N, N + 1, 5 * step}
+    assert [(c.N, c.f, c.p, c.mode, c.window) for c in R if c.group == "parity"] == pu.PARITY_CASES
+    assert len({pu.replay_id(c) for c in R}) == len(R)
+    for c in R:
+        g = pu.geometry(c.N, c.f, c.p, c.L)
+        assert g["step"] >= 1 and g["hops"] <= 520 and (c.N < 16384 or (c.ch == 2 and g["hops"] <= 200)), (c, g)
+        assert c.group in ("edge", "parity", "class") or 6 * c.N <= c.L <= 13 * c.N, c
     ns = {c[0] for c in pu.PARITY_CASES}
     assert {32, 512, 16384} <= ns
     assert {1, 2} <= {c[2] for c in pu.PARITY_CASES} and any(c[2] < 0 for c in pu.PARITY_CASES)
@@ -216,3 +240,138 @@ def test_parity_cases_cover_what_the_gpu_test_must():
         if c[4] is not None:
             w = windowutil.WINDOWS[c[4]](c[0])
             assert not np.array_equal(w, w[::-1])  # asymmetric
+
+
+# ------------------------------------------------------------------------------------------------ replay: the verifiers verified
+def _case(**want):
+    hit = [c for c in pu.REPLAY_CASES if all(getattr(c, k) == v for k, v in want.items())]
+    assert hit, want
+    return hit[0]
+
+
+def _twin_rows(c, **kw):
+    x = pu.replay_input(c)
+    w = pu.case_window(c.N, c.window)
+    return x, w, pu.replay_twin(x, c.N, c.f, c.p, c.mode, window=w, **kw)
+
+
+@pytest.mark.parametrize("case", pu.REPLAY_CASES, ids=pu.replay_id)
+def test_the_twins_stage_rows_pass_every_verifier(case):
+    """Before any GPU is involved: the definition, every stage rounded to float32 before the next one reads it, passes all
+    five verifiers on every replay case. The figures printed are the slack the gates leave over float32 storage alone;
+    the excused share is a property of the input and stays under the cap."""
+    x, w, rows = _twin_rows(case)
+    fig = pu.verify(rows, x, case.N, case.f, case.p, case.mode, window=w, what=pu.replay_id(case))
+    assert fig["S2"]["share"] <= pu.EXCUSED_CAP
+    assert fig["S2"]["worst"] == 0  # the twin's turns are the verifier's: the increments are exact
+    for s in ("S1", "S4", "S5"):
+        assert fig[s]["worst"] <= pu.REG_TOL / 20, (s, fig[s])
+
+
+@pytest.mark.parametrize("case", [pu.PARITY_CASES[3], pu.PARITY_CASES[5], pu.PARITY_CASES[7]], ids=str)
+def test_the_staged_twin_is_the_definition(case):
+    """replay_twin against stretch() on well-conditioned cases: float32 storage between the stages moves the output by
+    less than the conditioning check allows a 2^-22 perturbation to"""
+    N, f, p, mode, wname = case
+    x = pu.case_input(N)
+    rows = pu.replay_twin(x, N, f, p, mode, window=pu.case_window(N, wname))
+    ref = pu.stretch(x, N, f, p, mode, window=pu.case_window(N, wname))
+    assert rows.out.shape == ref.shape
+    err = pu.rel_rms(rows.out, ref)
+    print(f"{case}: staged twin against the definition {err:.2e}")
+    assert err <= pu.PERTURB_TOL
+
+
+def test_peak_flags_are_the_peaks_of_every_row():
+    rng = np.random.default_rng(3)
+    m2 = rng.integers(0, 4, (40, 33)).astype(np.float32)  # (a narrow range: plateaus and ties at distance 2)
+    flags = pu.peak_flags(m2)
+    for r in range(m2.shape[0]):
+        assert list(np.flatnonzero(flags[r])) == list(pu.peaks(m2[r]))
+    assert flags.any() and not flags[:, 0].any() and not flags[:, -1].any()
+
+
+@pytest.mark.parametrize("step", [128, 64, 16, 85, 25, 170, 341])
+def test_the_lattice_holds_every_pair_of_turns_within_the_bound(step):
+    """lattice_ok accepts the increment of ANY turns within TURN_BOUND of the given ones - so it can fail no correct kernel -
+    and, where H / step - 1 exceeds 1, refuses most increments that are one unit off"""
+    N, H = 256, 128
+    rng = np.random.default_rng(step)
+    hit = total = 0
+    for _ in range(200):
+        a0, a1 = rng.integers(0, 1 << 32, H + 1), rng.integers(0, 1 << 32, H + 1)
+        d0, d1 = (rng.integers(-pu.TURN_BOUND, pu.TURN_BOUND + 1, H + 1) for _ in range(2))
+        far = np.abs(pu.deviation(a0, a1, N, step)) < (1 << 31) - (1 << 11)  # (the bins S2 does not excuse)
+        e = pu.increments((a0 + d0) & pu.MASK, (a1 + d1) & pu.MASK, N, step)
+        ok = pu.lattice_ok(e, a0, a1, N, step)
+        assert ok is not None and ok[far | (H % step == 0)].all()
+        off = pu.lattice_ok((e + 1) & pu.MASK, a0, a1, N, step)
+        hit += int((~off[far]).sum())
+        total += int(far.sum())
+    ratio = H / step
+    print(f"step {step}: H / step = {ratio:.3f}, one unit off is refused at {hit / total:.1%} of the bins")
+    if ratio - 1 >= 2 or (H % step == 0 and ratio >= 3):
+        assert hit / total >= 0.4
+
+
+MUTANT_CASES = {
+    "upper_on_tie": dict(group="channels", N=256, mode=pu.LOCKED, ch=3),
+    "no_odd_term": dict(group="window", N=32, mode=pu.PROPAGATE),
+    "truncate": dict(group="window", N=512, f=5.0, mode=pu.PROPAGATE),  # H / step = 5.02: the lattice is sparse
+    "halo_ignored": dict(group="edge", N=256, L=320, mode=pu.PROPAGATE),
+    "minus_theta": dict(group="factor", f=3.0, mode=pu.LOCKED),
+    "no_conjugate": dict(group="window", N=64, mode=pu.PROPAGATE),
+    "plain_envelope": dict(group="caller", N=256, window="skew", mode=pu.LOCKED),
+    "channel0_theta": dict(group="channels", N=64, ch=2),
+}
+
+
+@pytest.mark.parametrize("mutant", pu.MUTANTS)
+def test_every_mutant_is_caught_by_the_stage_that_owns_it(mutant):
+    """The stages in front of the owner pass (verify runs them in order and stops at the first finding), the owner
+    refuses, and says by how much. "truncate" moves an increment by ONE unit of 2^-32 turn at negative dev: the tolerance
+    of S2 cannot see that - its exact half, the lattice, does wherever H / step - 1 exceeds 1."""
+    c = _case(**MUTANT_CASES[mutant])
+    g = pu.geometry(c.N, c.f, c.p, c.L)
+    x, w, rows = _twin_rows(c, mutant=mutant, chunk=g["hpw"])
+    with pytest.raises(pu.StageError) as ei:
+        pu.verify(rows, x, c.N, c.f, c.p, c.mode, window=w, what=pu.replay_id(c))
+    print(f"MUTANT {mutant} on {pu.replay_id(c)}: {ei.value}")
+    assert ei.value.stage == pu.OWNER_OF_MUTANT[mutant], ei.value
+    assert "excused" not in str(ei.value)  # (refused for what it computes, not for its input)
+
+
+def test_clicks_tie_and_are_not_admissible_under_locked():
+    """What LOCKED cannot take: the spectrum of two clicks is a cosine in the bin index, its maxima are
+    plateaus and mirror pairs in float32, and the owner of a large share of the bins depends on which float32 evaluation
+    of re^2 + im^2 a compiler picks. The verifier says so itself instead of passing or failing by luck; white input has
+    no such bin."""
+    c = _case(signal="comb", N=2048)
+    x = pu.replay_input(c)
+    rows = pu.replay_twin(x, c.N, c.f, c.p, pu.LOCKED)
+    g = pu.geometry(c.N, c.f, c.p, c.L)
+    fig = pu.verify_theta(rows.X, rows.theta, c.N, g["step"], True)
+    print(f"two clicks under LOCKED: {fig['share']:.1%} of the bins are excused (cap {pu.EXCUSED_CAP:.1%})")
+    assert fig["share"] > 10 * pu.EXCUSED_CAP
+    with pytest.raises(pu.StageError, match="not admissible"):
+        pu.verify(rows, x, c.N, c.f, c.p, pu.LOCKED, what="comb under LOCKED", stages=("S2",))
+    w = _case(signal="white_full", N=2048, mode=pu.LOCKED)
+    xw, _w, rw = _twin_rows(w)
+    assert pu.verify_theta(rw.X, rw.theta, w.N, pu.geometry(w.N, w.f, w.p, w.L)["step"], True)["excused"] == 0
+
+
+def test_a_hop_under_the_windows_edge_is_above_the_gate_for_any_float32_transform():
+    """Why S4 holds single hops to the C oracle's figure instead of REG_TOL: the last samples of a burst at the start of a
+    frame leave a row whose windowed RMS is a few percent of the unwindowed one, and a float32 inverse transform - the
+    reference's own, here - misses REG_TOL relative to the windowed row. Every ordinary hop is 20 times inside the gate."""
+    c = _case(signal="bursts", N=2048, mode=pu.LOCKED)
+    _x, _w, rows = _twin_rows(c)
+    w32 = pu.window_of(c.N, None)
+    raw = np.fft.ifft(rows.Z[0].astype(np.complex128), axis=-1).real
+    live = np.flatnonzero(np.abs(raw).max(axis=-1) > 0)
+    kept = np.sqrt(np.mean((raw[live] * w32) ** 2, axis=-1) / np.mean(raw[live] ** 2, axis=-1))
+    edge, usual = live[kept.argmin()], live[np.argsort(kept)[live.size // 2]]
+    fig_edge, fig_usual = pu.oracle_synthesis_figure(rows.Z[0, edge], w32), pu.oracle_synthesis_figure(rows.Z[0, usual], w32)
+    print(f"hop {edge}: {kept.min():.1%} of the RMS survives the window, the C oracle's float32 transform is {fig_edge:.2e} from float64; "
+          f"hop {usual}: {fig_usual:.2e}")
+    assert kept.min() < 0.05 and fig_edge > pu.REG_TOL and fig_usual < pu.REG_TOL / 10

@@ -18,7 +18,8 @@ def test_engine_phase_host_code_runs_clean(target, env, marker):
     """Against numbers written out by hand: the launches of every chunk of a three-chunk job in order - analysis with the
     halo hop, prep, scan, walk, apply, the phase-keeping synthesis, the overlap-add; theta zeroed at hop 0 and carried from
     chunk to chunk, call after call; the coherent envelope and the plain amplitude under a mode, the reference's bits again
-    behind RANDOM; every refusal in both orders of the two calls."""
+    behind RANDOM; every refusal in both orders of the two calls; the rows and the chunk table rc_test_phase_tap copies
+    out, into arrays of exactly their size, and its refusal of a job that does not fit."""
     exe = _build(target)
     r = subprocess.run([exe], env=dict(os.environ, **env), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
