@@ -38,6 +38,28 @@ extern "C" {
 #define RC_ECAPACITY (-6)  /* caller buffer too small */
 
 /*
+ * The channel count, and what bounds it on each path (DESIGN "Parity across channel counts"):
+ *   fused kernels, N = 32 ... 65536   the launch is runs_per_channel x channels workgroups in grid.x, a 32-bit product
+ *                                     that the run planner keeps at max(channels, a few rounds of the resident
+ *                                     workgroups): 2^31 - 1 by itself. The tail staging in front of every range, ragged
+ *                                     last hop and streaming batch (prep_kernel) has the channels in grid.y: 65535.
+ *   unfused (host / device kernel, negative pitch), chirp-z lengths, frames stages
+ *                                     channels in grid.y or grid.z of the overlap-add, tail, chirp-z, resampling and
+ *                                     frames launches: 65535. One chunk holds at least one window of every channel:
+ *                                     channels x hops_per_window x 12 ... 28 N bytes of scratch (RC_ENOMEM beyond HBM).
+ *   long windows, N > 65536           channels in grid.z: 65535; a chunk of one window takes channels x 2 x 20 N bytes.
+ *   phase key                         the channel index above bit 40 of a 64-bit counter: 2^24 channels.
+ *   every path                        channels x N / 2 floats of overlap tail per engine.
+ * RC_MAX_CHANNELS is the smallest of them. rc_derive_params, rc_offline_output_len (0) and rc_engine_create refuse a larger
+ * count with RC_EUNSUPPORTED before anything is allocated; rc_last_error() names the limit.
+ * RC_MAX_JOB_HOPS: the hops of one call over all its channels (hops x channels). The kernels' flat hop indices and the run
+ * tables are 32-bit words. Only a job knows its hops: every entry that runs hops (whole jobs, ranges, streaming batches,
+ * rc_multi shards) returns RC_EUNSUPPORTED for a larger product before it enqueues a launch.
+ */
+#define RC_MAX_CHANNELS 65535u
+#define RC_MAX_JOB_HOPS 4294967295ull
+
+/*
  * User frequency kernel. C-ABI shape of the reference's hot-swapped
  *   #[no_mangle] pub fn apply(elapsed_ms: usize, input: Vec<(f32,f32)>) -> Vec<(f32,f32)>
  * (README.md:106-112; resolved and called at src/fft.rs:93-95). `in_reim`/`out_reim` hold
@@ -57,7 +79,7 @@ typedef struct rc_config {
     float amplitude;         /* -a/--amplitude */
     int32_t pitch_multiple;  /* -p/--pitch_multiple, i8 in the reference, != 0 */
     uint32_t sample_rate;    /* AudioSpec.sample_rate (src/audio.rs:31-37) */
-    uint32_t channels;       /* AudioSpec.channels: one Stretcher per channel (main.rs:133) */
+    uint32_t channels;       /* AudioSpec.channels: one Stretcher per channel (main.rs:133); 1 ... RC_MAX_CHANNELS (below) */
     float buffer_secs;       /* -b/--buffer (Duration, default 1 s) */
     uint64_t seed;           /* phase-source seed (replaces thread_rng, src/fft.rs:64) */
     int32_t device;          /* HIP device ordinal */

@@ -349,6 +349,32 @@ int main() {
     CHECK(rc_engine_create(&bad, &e) == RC_EINVAL && e == nullptr);
     bad = config(1001, 2.0f, 1, 1);  // odd length
     CHECK(rc_engine_create(&bad, &e) != RC_OK);
+    // the channel limit: refused by name at the creation, on every window path; RC_MAX_CHANNELS itself is taken
+    for (uint32_t N : {64u, 16384u, 65536u, 3000u, 131072u}) {
+        bad = config(N, 2.0f, 1, 1);
+        bad.channels = RC_MAX_CHANNELS + 1;
+        CHECK(rc_engine_create(&bad, &e) == RC_EUNSUPPORTED && e == nullptr);
+        CHECK(strstr(rc_last_error(), "RC_MAX_CHANNELS = 65535") != nullptr);
+    }
+    {  // ... and a job of more than RC_MAX_JOB_HOPS hops over its channels at the entry: 65535 channels of 65538 hops. The
+       // rows are four floats long, whatever the call says: a refusal that came after the first read or write would be ASan's
+        rc_config c = config(32, 16.0f, 1, 1);
+        c.channels = RC_MAX_CHANNELS;
+        CHECK(rc_engine_create(&c, &e) == RC_OK && e);
+        const size_t L = 32 + 65536, n_out = rc_offline_output_len(&c, L);
+        CHECK(n_out == (size_t)32769 * 32);
+        void *d_in = nullptr, *d_out = nullptr;
+        CHECK(hipMalloc(&d_in, 16) == 0 && hipMalloc(&d_out, 16) == 0);
+        size_t got = 0;
+        CHECK(rc_engine_stretch_device(e, (const float *)d_in, 0, L, (float *)d_out, 0, n_out, &got, nullptr) == RC_EUNSUPPORTED);
+        CHECK(strstr(rc_last_error(), "RC_MAX_JOB_HOPS") != nullptr && strstr(rc_last_error(), "4294967295") != nullptr);
+        CHECK(rc_engine_stretch_device_range(e, (const float *)d_in, 0, L, 0, RC_MAX_CHANNELS, 0, 32769, (float *)d_out, 0, n_out, nullptr) ==
+              RC_EUNSUPPORTED);
+        CHECK(rc_engine_synchronize(e) == RC_OK);
+        CHECK(hipFree(d_in) == 0 && hipFree(d_out) == 0);
+        rc_engine_destroy(e);
+        e = nullptr;
+    }
     float ms = 0, ns = 0;
     CHECK(rc_calib_valu(0, nullptr, 2, &ms, &ns) == RC_OK);
     printf("OK engine host driver (%ld kernel calls)\n", g_calls.load());
